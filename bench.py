@@ -3,6 +3,12 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config rtow|cornell|rtow4k|mesh50k|sample_scene]
                     [--precision f64|f32] [--no-cpu-baseline] [--no-end-to-end] [--no-pmc]
                     [--mp-mode ranks|inproc] [--dist-backend nccl|gloo] [--dump frame.npz]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is
+given, and prints the result line (metric, value, ms_per_step, the trace step's HIP-event time).  --full
+adds everything else described below: the CPU baselines, the work counters and rooflines, the
+end-to-end renders, the 16 progressive batches of --mp-mode inproc.
 
 A "step" renders one full frame of the workload: every pixel x every sample, traced on the GPU(s)
 from a scene already resident in HBM, the per-pixel float64 sums RCCL-reduced to rank 0 (N>1), and
@@ -20,7 +26,7 @@ N > 1, two ways, both runnable as a plain `python bench.py --gpus 
       also carries `progressive_16`: the same with the Node default of 16 progressive batches.
 
 Prints ONE JSON line on rank 0 (driver contract).  The trace step's duration comes from HIP events
-recorded inside librt_hip.so on the stream the kernels run on.  At N=1 (unless --no-pmc) rank 0 then
+recorded inside librt_hip.so on the stream the kernels run on.  With --full at N=1 (unless --no-pmc) rank 0 then
 re-runs one frame of the same workload under rocprofv3 three times — FETCH_SIZE, WRITE_SIZE and eight
 SQ counters, each pass in its own process — so `roofline` (measured HBM bytes, bound "hbm") and
 `roofline_binding` (VALU issue slots and lane utilization, the resource that binds) are measured by
@@ -86,6 +92,15 @@ def parse():
                          "0 (default): one reduce after the trace (DESIGN.md §6: the one-GPU rehearsal measured the "
                          "banded trace 1.1 %% slower, and the RCCL kernels cannot run beside the persistent trace waves)")
     ap.add_argument("--dump", help="rank 0 writes the frame's float64 sums and RGBA8 here (.npz) after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="rank 0 writes what the last timed step delivered as DIR/<name>.npy (float64 sums, float32 "
+                         "post-gamma frame and RGBA8; a fixed seeded sample of the pixels when the frame is larger "
+                         "than DUMP_BUDGET)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the bench measures: the CPU baselines, the "
+                         "work counters and rooflines (one more frame, the rocprofv3 counter passes, the instruction "
+                         "floor), the end-to-end renders from Python and Node, and with --mp-mode inproc the 16 "
+                         "progressive batches; --no-cpu-baseline / --no-end-to-end / --no-pmc leave parts of it out")
     return ap.parse_args()
 
 
@@ -335,6 +350,28 @@ def build_provenance():
             "library_matches_tree": info.get("source_digest") == tree}
 
 
+DUMP_BUDGET = 48 << 20      # bytes --dump-outputs may write in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> one row per pixel) as outdir/<name>.npy, float64
+    kept, everything else as float32.  A frame over DUMP_BUDGET is cut to the same seeded sample of its
+    pixels in every array (the same pixels in every run of the same frame size), whose indices go to
+    pixel_index.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.itemsize * a[0].size for a in arrays.values()) + 8
+    if n * row_bytes > DUMP_BUDGET:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_BUDGET // row_bytes, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N rank processes (RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment, as torch.distributed.run sets them) and wait for them.
@@ -397,7 +434,7 @@ def main():
                             for k, o in zip(packed.kinds, packed.objects))
 
     cpu = None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(rt, args.config, cfg, args.seed, args.cpu_crop)
 
     inproc_devices = [k % ndev for k in range(args.gpus)] if inproc else None
@@ -434,7 +471,66 @@ def main():
     if distributed:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
-    # the work counters of the frame (identical in every step): one more, untimed step with stats
+    if rank == 0 and (args.dump or args.dump_outputs):
+        # what the last timed step left: ranks: the reduced float64 sums and rank 0's epilogue (Float32
+        # post-gamma frame, RGBA8) in device memory; inproc: rt_render's RGBA8 on the host, and its
+        # checkpoint holds the frame's merged float64 sums
+        import numpy as np
+        if inproc:
+            sums, done = rt.checkpoint()
+            frame = {"sum": sums.reshape(-1, 3), "rgba8": job.rgba8.reshape(-1, 4)}
+        else:
+            done = job.samples
+            frame = {"sum": job.sum.cpu().numpy().reshape(-1, 3), "post": job.post.cpu().numpy().reshape(-1, 4),
+                     "rgba8": job.rgba8.cpu().numpy().reshape(-1, 4)}
+        if args.dump:
+            np.savez(args.dump, sum=frame["sum"].reshape(-1), rgba8=frame["rgba8"].reshape(-1), samples=done)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame)
+        del frame
+    if distributed:
+        mp_mode = {"mode": "ranks", "world_size": dist.get_world_size(), "backend": dist.get_backend(),
+                   "launcher": "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "bench.py spawn",
+                   "reduce_bands": job.bands}
+        parallelism = (f"sample-split x{world} + RCCL reduce" if args.dist_backend == "nccl" and world > 1 else
+                       "1 GPU, RCCL reduce at world size 1" if args.dist_backend == "nccl" else
+                       f"REHEARSAL sample-split x{world} over {ndev} GPU(s), gloo host reduce: not a measurement")
+    elif inproc:
+        mp_mode = {"mode": "inproc", "devices": inproc_devices}
+        parallelism = (f"in-process whole-batch split x{args.gpus} (rt_settings.devices {inproc_devices}: batch k "
+                       "on device k % N, chunk partials copied over xGMI and reduced in batch order on device 0)" +
+                       ("" if len(set(inproc_devices)) == args.gpus else
+                        f": REHEARSAL on {ndev} GPU(s), not a measurement"))
+    else:
+        mp_mode = None
+        parallelism = "1 GPU"
+    rank_samples = cfg["w"] * cfg["h"] * (job.range[1] - job.range[0])
+    k_ms = sum(kernel_ms) / len(kernel_ms)
+    line = {
+        "metric": METRIC, "value": round(cfg["w"] * cfg["h"] * rt.settings().samples * args.steps / elapsed / 1e6, 3),
+        "unit": "Msamples/s", "n_gpus": args.gpus,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": args.precision,
+        "data": "synthetic",
+        "config": {"workload": f"config{cfg['cfg']}_{args.config}_{cfg['w']}x{cfg['h']}_{cfg['spp']}spp",
+                   "scene": cfg["scene"], "width": cfg["w"], "height": cfg["h"], "spp": cfg["spp"],
+                   "max_depth": cfg["depth"], "primitives": packed.primitives_per_segment(), "accel": args.accel,
+                   "parallelism": parallelism},
+        "mp_mode": mp_mode,
+        "kernel_ms": round(k_ms, 3),
+        "kernel_msamples_per_s": round(rank_samples / (k_ms * 1e-3) / 1e6, 3),
+        "full": args.full,
+        "build": build_provenance(),
+    }
+    if not args.full:
+        # the plain run ends here: set-up, warm-up, the timed steps, their outputs, the result line
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if distributed:
+            dist.destroy_process_group()
+        return
+    # --full from here on.  The work counters of the frame (identical in every step): one more, untimed
+    # step with stats
     job.step()
     torch.cuda.synchronize()
     segs, abytes = [job.stats.segments], [job.stats.algorithmic_bytes]
@@ -456,15 +552,6 @@ def main():
                        "what": "rt_render with rt_settings.devices as the Node drop-in ships it: 16 sample batches "
                                "dealt round-robin to the devices, the running frame into a preview buffer and a "
                                "progress callback after each batch"}
-    if args.dump and rank == 0:
-        import numpy as np
-        torch.cuda.synchronize()
-        if inproc:      # rt_render's checkpoint holds the frame's merged float64 sums
-            sums, done = rt.checkpoint()
-            np.savez(args.dump, sum=sums.reshape(-1), rgba8=job.rgba8, samples=done)
-        else:
-            np.savez(args.dump, sum=job.sum.cpu().numpy(), rgba8=job.rgba8.cpu().numpy(), samples=job.samples)
-
     e2e = e2e_node = None
     if rank == 0 and args.gpus == 1 and not args.no_end_to_end:
         # RayTracer.render as the drop-in boundary runs it (rt_render): sums zeroed on device, the
@@ -479,9 +566,6 @@ def main():
         e2e_node = node_end_to_end(cfg, args)
 
     if rank == 0:
-        total_samples = cfg["w"] * cfg["h"] * rt.settings().samples * args.steps
-        value = total_samples / elapsed / 1e6
-        k_ms = sum(kernel_ms) / len(kernel_ms)
         a_bytes = sum(abytes) / len(abytes)
         seg_launch = sum(segs) / len(segs)
         nodes, sph, tri = (sum(w[k] for w in work) / len(work) for k in range(3))
@@ -491,7 +575,6 @@ def main():
             flops = 12 * nodes + FLOPS["sphere"] * sph + FLOPS["triangle"] * tri + seg_launch * brute
         else:
             flops = seg_launch * flops_per_segment
-        rank_samples = cfg["w"] * cfg["h"] * (job.range[1] - job.range[0])
         # the walk this render ran (rt_scene_walk): BVH nodes or grid cells are its walk steps
         walk = {0: "world_order", 1: "bvh", 2: "uniform_grid"}.get(
             capi.load_library().rt_scene_walk(rt.scene_handle(), capi.RT_PREC_F32 if args.precision == "f32" else capi.RT_PREC_F64,
@@ -588,32 +671,8 @@ def main():
             "walk": walk,
             "walk_steps_per_segment": round(nodes / seg_launch, 3) if bvh else None,
             "prim_tests_per_segment": round((sph + tri) / seg_launch, 3) if bvh else None})
-        if distributed:
-            mp_mode = {"mode": "ranks", "world_size": dist.get_world_size(), "backend": dist.get_backend(),
-                       "launcher": "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "bench.py spawn",
-                       "reduce_bands": job.bands}
-            parallelism = (f"sample-split x{world} + RCCL reduce" if args.dist_backend == "nccl" and world > 1 else
-                           "1 GPU, RCCL reduce at world size 1" if args.dist_backend == "nccl" else
-                           f"REHEARSAL sample-split x{world} over {ndev} GPU(s), gloo host reduce: not a measurement")
-        elif inproc:
-            mp_mode = {"mode": "inproc", "devices": inproc_devices}
-            parallelism = (f"in-process whole-batch split x{args.gpus} (rt_settings.devices {inproc_devices}: batch k "
-                           "on device k % N, chunk partials copied over xGMI and reduced in batch order on device 0)" +
-                           ("" if len(set(inproc_devices)) == args.gpus else
-                            f": REHEARSAL on {ndev} GPU(s), not a measurement"))
-        else:
-            mp_mode = None
-            parallelism = "1 GPU"
-        line = {
-            "metric": METRIC, "value": round(value, 3), "unit": "Msamples/s", "n_gpus": args.gpus,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": args.precision,
-            "data": "synthetic",
-            "config": {"workload": f"config{cfg['cfg']}_{args.config}_{cfg['w']}x{cfg['h']}_{cfg['spp']}spp",
-                       "scene": cfg["scene"], "width": cfg["w"], "height": cfg["h"], "spp": cfg["spp"],
-                       "max_depth": cfg["depth"], "primitives": packed.primitives_per_segment(), "accel": args.accel,
-                       "parallelism": parallelism},
-            "mp_mode": mp_mode,
+        build = line.pop("build")
+        line.update({
             "progressive_16": progressive,
             "roofline": roofline,
             "roofline_binding": binding if binding is not None else ({"floor": floor} if floor else None),
@@ -623,12 +682,11 @@ def main():
                            "flops_per_segment": round(flops / seg_launch, 2),
                            "definition": "SURVEY 8d canonical flops (12/node, 23/sphere, 51/triangle test)"},
             "segments_per_sample": round(seg_launch / rank_samples, 4),
-            "kernel_msamples_per_s": round(rank_samples / (k_ms * 1e-3) / 1e6, 3),
             "cpu_baseline": cpu,
             "end_to_end": e2e,
             "end_to_end_node": e2e_node,
-            "build": build_provenance(),
-        }
+            "build": build,
+        })
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()

@@ -9,6 +9,6 @@ tag=$1; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o run -- python3 bench.py --no-cpu-baseline --no-pmc "$@" > $out/bench_under_trace.log 2>&1 || exit $?
-BENCH_PMC_KEEP=$out/pmc timeout -k 10 600 python3 bench.py --no-cpu-baseline --no-end-to-end "$@" > $out/bench.json 2> $out/bench.err || exit $?
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o run -- python3 bench.py --full --no-cpu-baseline --no-pmc "$@" > $out/bench_under_trace.log 2>&1 || exit $?
+BENCH_PMC_KEEP=$out/pmc timeout -k 10 600 python3 bench.py --full --no-cpu-baseline --no-end-to-end "$@" > $out/bench.json 2> $out/bench.err || exit $?
 tail -1 $out/bench.json

@@ -1012,7 +1012,7 @@ def test_bench_multi_rank_rehearsal(gpu, tmp_path, world, launch):
     elif launch == "spawn":
         cmd = [sys.executable, bench, "--gpus", str(world), "--dist-backend", "gloo", *common, *dump]
     else:
-        cmd = [sys.executable, bench, "--gpus", str(world), "--mp-mode", "inproc", *common, *dump]
+        cmd = [sys.executable, bench, "--gpus", str(world), "--mp-mode", "inproc", "--full", *common, *dump]   # progressive_16
     multi = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert multi.returncode == 0, multi.stderr[-3000:]
     line = json.loads([ln for ln in multi.stdout.splitlines() if ln.startswith("{")][-1])
