@@ -9,7 +9,8 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "librt_hip.so")
 
-RT_ABI_VERSION = 3
+RT_ABI_VERSION = 3            # rt_abi_version()
+RT_DESC_TEXTURES = 0x54455834  # rt_scene_desc.extensions of a descriptor whose texture fields are filled
 RT_MAX_DEVICES = 8
 
 # enums (include/rt_hip.h)
@@ -22,6 +23,7 @@ RT_TM_REINHARD, RT_TM_ACES, RT_TM_LINEAR = range(3)
 RT_PREC_F64, RT_PREC_F32 = range(2)
 RT_ACCEL_AUTO, RT_ACCEL_BRUTE, RT_ACCEL_BVH = range(3)
 RT_SUM_POOL, RT_SUM_SAMPLE_ORDER = range(2)
+RT_TEX_CHECKER, RT_TEX_NOISE, RT_TEX_MARBLE, RT_TEX_WOOD = range(4)
 
 STATUS = {0: "RT_OK", -1: "RT_ERR_INVALID", -2: "RT_ERR_DEVICE", -3: "RT_ERR_NOMEM",
           -4: "RT_ERR_CANCELLED", -5: "RT_ERR_NO_DEVICE"}
@@ -37,6 +39,11 @@ class ObjectDesc(C.Structure):
                 ("count", C.c_int32), ("g", C.c_double * 6)]
 
 
+class TextureDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("perm", C.c_int32), ("scale", C.c_double), ("odd", C.c_double * 3),
+                ("even", C.c_double * 3)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("lower_left", C.c_double * 3), ("horizontal", C.c_double * 3),
                 ("vertical", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3),
@@ -47,8 +54,11 @@ class SceneDesc(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("num_objects", C.c_int32), ("objects", C.POINTER(ObjectDesc)),
                 ("num_materials", C.c_int32), ("num_triangles", C.c_int32),
                 ("materials", C.POINTER(MaterialDesc)), ("triangles", C.POINTER(C.c_double)),
-                ("camera", CameraDesc), ("background", C.c_int32), ("_pad", C.c_int32),
-                ("sky_intensity", C.c_double), ("solid_color", C.c_double * 3), ("perm", C.c_int32 * 512)]
+                ("camera", CameraDesc), ("background", C.c_int32), ("extensions", C.c_int32),
+                ("sky_intensity", C.c_double), ("solid_color", C.c_double * 3), ("perm", C.c_int32 * 512),
+                ("num_textures", C.c_int32), ("num_texture_perms", C.c_int32),
+                ("textures", C.POINTER(TextureDesc)), ("material_texture", C.POINTER(C.c_int32)),
+                ("texture_perms", C.POINTER(C.c_int32))]
 
 
 class Settings(C.Structure):
@@ -95,6 +105,8 @@ EXPORTS = {
     "rt_cancel": (C.c_int, [C.c_void_p]),
     "rt_closest_hits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_size_t,
                                   C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rt_texture_values": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_size_t,
+                                    C.POINTER(C.c_double)]),
     "rt_scene_walk": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "rt_render_checkpoint": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_int32)]),
     "rt_render_resume": (C.c_int, [C.c_void_p, C.POINTER(Settings), C.POINTER(C.c_double), C.c_int32,

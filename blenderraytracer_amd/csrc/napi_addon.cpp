@@ -156,6 +156,7 @@ napi_value create_scene(napi_env env, napi_callback_info info) {
     rt_scene_desc desc;
     std::memset(&desc, 0, sizeof desc);
     desc.abi_version = RT_ABI_VERSION;
+    desc.extensions = RT_DESC_TEXTURES;            // the texture fields are filled below (zero: none)
     void* p;
     size_t n;
     if (get_bytes(env, d, "objects", &p, &n)) {
@@ -188,6 +189,22 @@ napi_value create_scene(napi_env env, napi_callback_info info) {
     if (!get_bytes(env, d, "perm", &p, &n) || n != 512 * sizeof(int32_t))
         return throw_err(env, "desc.perm must be an Int32Array(512) (World.cloudNoise.p)");
     std::memcpy(desc.perm, p, sizeof desc.perm);
+    // procedural textures (pack.mjs): rt_texture_desc records, one Int32 per material, 512 Int32 per table;
+    // all three optional (a plain scene)
+    if (get_bytes(env, d, "textures", &p, &n) && n >= sizeof(rt_texture_desc)) {
+        desc.textures = static_cast<const rt_texture_desc*>(p);
+        desc.num_textures = (int32_t)(n / sizeof(rt_texture_desc));
+    }
+    if (get_bytes(env, d, "materialTexture", &p, &n) && n > 0) {
+        if (n != (size_t)desc.num_materials * sizeof(int32_t))
+            return throw_err(env, "desc.materialTexture must hold one Int32 per material");
+        desc.material_texture = static_cast<const int32_t*>(p);
+    }
+    if (get_bytes(env, d, "texturePerms", &p, &n) && n > 0) {
+        if (n % (512 * sizeof(int32_t))) return throw_err(env, "desc.texturePerms must hold 512 Int32 per table");
+        desc.texture_perms = static_cast<const int32_t*>(p);
+        desc.num_texture_perms = (int32_t)(n / (512 * sizeof(int32_t)));
+    }
     rt_scene* sc = nullptr;
     if (rt_scene_create(&desc, device, &sc) != RT_OK) return throw_err(env, std::string("rt_scene_create: ") + rt_last_error());
     SceneBox* box = new SceneBox();

@@ -240,6 +240,13 @@ struct Bvh2Node { float lo[3][2]; float hi[3][2]; int child[2]; int pad[2]; };
 #define RT_BVH_STACK 24           // 6 KB of LDS per one-wave workgroup; trees up to ~16.7M primitives
 #endif
 
+// Procedural textures (textures.js:24-81): one record per distinct texture object.  `perm` is the index of
+// the texture's own PerlinNoise table (512 ints each) in TexView::perms, -1 for the checker.
+enum TexType : int { TEX_CHECKER = 0, TEX_NOISE = 1, TEX_MARBLE = 2, TEX_WOOD = 3 };
+template <class R> struct TexRec { int type, perm; R scale; R odd[3], even[3]; };
+// Everything a textured scene adds, behind SceneView::tex: mat_tex[m] = the texture of material m, -1 none
+template <class R> struct TexView { const TexRec<R>* recs; const int* perms; const int* mat_tex; int num, num_perms; };
+
 template <class R>
 struct SceneView {
     const Run* runs;
@@ -259,7 +266,10 @@ struct SceneView {
     const int* tri_mat;            // per triangle (mesh triangles carry the mesh's material)
     const MatRec<R>* mats;
     int num_mats;
-    const int* perm;               // World.cloudNoise.p[512]
+    int num_tex;                   // procedural textures (0: none; only then do the F_TEX kernels run).  It fills
+                                   // the 4 padding bytes before `perm`: no other field moves (static_assert below)
+    const int* perm;               // World.cloudNoise.p[512]; with num_tex > 0 followed by the scene's TexView
+                                   // (tex_view): all texture state sits behind this one pointer
     // acceleration structure (closest_hit_bvh): planes and boxes are tested brute force with their
     // World.objects index, spheres and triangles through one BVH each over leaf-order copies
     int num_planes, num_boxes;
@@ -303,6 +313,14 @@ struct SceneView {
     R sky_intensity;
     R solid[3];
 };
+// num_tex sits in what was padding: the kernel-argument layout of every kernel is the one it had without it
+static_assert(offsetof(SceneView<double>, perm) == offsetof(SceneView<double>, num_mats) + 8 &&
+              offsetof(SceneView<float>, perm) == offsetof(SceneView<float>, num_mats) + 8, "num_tex fills padding");
+// the TexView of a textured scene, stored behind the world's 512-entry table (2048 B: 8-aligned)
+constexpr int kTexViewAt = 512;
+template <class R> RT_HD const TexView<R>* tex_view(const SceneView<R>& sc) {
+    return reinterpret_cast<const TexView<R>*>(sc.perm + kTexViewAt);
+}
 
 enum HitKind : int { HIT_NONE = -1, HIT_SPHERE = 0, HIT_PLANE = 1, HIT_BOX = 2, HIT_TRI = 3 };
 
@@ -463,7 +481,8 @@ RT_HD bool sphere_filter_pass(const SphereFilter& s, const FilterRay& r) {
 // only), the orthographic camera and the stochastic / centre AA modes (else the perspective camera with
 // supersampling).  A kernel compiled without a feature holds none of its code, nor the scene constants
 // that code reads, so fewer scalars stay live across the segment loop (SGPR spills).
-enum Feat : int { F_PLANES = 1, F_BOXES = 2, F_TRIS = 4, F_BGALL = 8, F_CAMALL = 16, F_ALL = 31 };
+enum Feat : int { F_PLANES = 1, F_BOXES = 2, F_TRIS = 4, F_BGALL = 8, F_CAMALL = 16, F_ALL = 31,
+                  F_TEX = 32 };   // F_TEX: textured Lambertian / Metal (not part of F_ALL: a kernel of its own)
 
 // Closest hit over the whole world: World.hit (world.js:20-33) with every object's hit() inlined.
 // All lanes walk the same primitive list in the same order, so every record load — including the
@@ -1292,9 +1311,15 @@ RT_HD Closest<R> closest_hit_grid(const SceneView<R>& sc, V3<R> o, V3<R> d, Work
 // ACC_GRID_LDS: the same walk with the grid's cell offsets and records (binary64: their filters) in LDS
 // ACC_BVH_TRI_LDS: the general ordered walk (scenes with triangles) with the triangle tree's top levels in
 // LDS (trace_pool_lds_kernel's persistent multi-wave workgroups, round 6)
+// ACC_BRUTE_TEX / ACC_BVH_STACK_TEX: World order / the general ordered walk for scenes with procedural
+// textures (F_ALL | F_TEX); every other mode is compiled without texture code
 enum Accel : int { ACC_BRUTE = 0, ACC_BRUTE_LEAN = 1, ACC_BVH = 2, ACC_BVH_STACK = 3, ACC_BVH_SPHERES = 4, ACC_BVH_SPHERES_LDS = 5,
                    ACC_GRID = 6, ACC_GRID_LDS = 7, ACC_BVH_TRI_LDS = 8, ACC_GRID_LDS_LEAN = 9,
-                   ACC_BVH_STACK_LEAN = 10 };
+                   ACC_BVH_STACK_LEAN = 10, ACC_BRUTE_TEX = 11, ACC_BVH_STACK_TEX = 12 };
+// the walk a mode runs (the textured modes walk like their untextured twins)
+template <int ACC> constexpr int walk_of() {
+    return ACC == ACC_BRUTE_TEX ? ACC_BRUTE : ACC == ACC_BVH_STACK_TEX ? ACC_BVH_STACK : ACC;
+}
 // The lean kernels (pt_trace.hip scene_feat): compiled for the common scene shapes only, the sky
 // gradient, the perspective camera and supersampling AA —
 //   ACC_GRID_LDS_LEAN: ACC_GRID_LDS for spheres alone (no planes, boxes or triangles; RTOW);
@@ -1302,7 +1327,7 @@ enum Accel : int { ACC_BRUTE = 0, ACC_BRUTE_LEAN = 1, ACC_BVH = 2, ACC_BVH_STACK
 //   ACC_BRUTE_LEAN: World order for spheres and planes (config 2's Cornell box)
 template <int ACC> constexpr int feat_of() {
     return ACC == ACC_GRID_LDS_LEAN ? 0 : ACC == ACC_BVH_STACK_LEAN ? (F_PLANES | F_TRIS)
-         : ACC == ACC_BRUTE_LEAN ? F_PLANES : F_ALL;
+         : ACC == ACC_BRUTE_LEAN ? F_PLANES : ACC == ACC_BRUTE_TEX || ACC == ACC_BVH_STACK_TEX ? (F_ALL | F_TEX) : F_ALL;
 }
 
 // RT_SC_RELOAD (bit mask of lean kernels: 1 tree, 2 grid, 4 brute force; default 2): the closest-hit
@@ -1334,7 +1359,8 @@ RT_HD Closest<R> closest_hit_acc(const SceneView<R>& sc, V3<R> o, V3<R> d, Work&
         return closest_hit_acc<R, ACC, true>(scl, o, d, w, stk, skip_tri, origin);
     }
 #endif
-    if constexpr (ACC == ACC_BVH) return closest_hit_bvh<R, false>(sc, o, d, w, stk, skip_tri);
+    if constexpr (walk_of<ACC>() != ACC) return closest_hit_acc<R, walk_of<ACC>(), LOCAL>(sc, o, d, w, stk, skip_tri, origin);
+    else if constexpr (ACC == ACC_BVH) return closest_hit_bvh<R, false>(sc, o, d, w, stk, skip_tri);
     else if constexpr (ACC == ACC_BVH_STACK) return closest_hit_bvh<R, true>(sc, o, d, w, stk, skip_tri);
     else if constexpr (ACC == ACC_BVH_SPHERES) return closest_hit_bvh<R, true, false>(sc, o, d, w, stk);
     else if constexpr (ACC == ACC_BVH_SPHERES_LDS) return closest_hit_bvh<R, true, false, true>(sc, o, d, w, stk);
@@ -1500,6 +1526,48 @@ __host__ __device__ V3<R> background(const SceneView<R>& sc, V3<R> d, V3<R> unit
     default:                                                                          // JSON solid/hdri bug
         return mk<R>((R)NAN, (R)NAN, (R)NAN);
     }
+}
+
+// ---- procedural textures (textures.js:24-81, noise.js:63-75) --------------------------------------
+// PerlinNoise.turbulence: accum += weight * noise(p); weight *= 0.5; p *= 2; Math.abs at the end
+template <class R>
+__host__ __device__ inline R turbulence(const int* perm, V3<R> q, int depth) {
+    R accum = 0, weight = 1;
+    for (int i = 0; i < depth; ++i) {
+        accum += weight * perlin<R>(perm, q.x, q.y, q.z);
+        weight *= (R)0.5;
+        q = q * (R)2;
+    }
+    return fabs(accum);
+}
+
+// Texture.value(u, v, p) of texture `tex` (u, v are never read).  Out of line like the cold backgrounds:
+// only the F_TEX kernels call it, once per textured hit, and it stays out of their walk's allocation.
+// Binary64: the reference's operations in its order with V8's Math.sin (js_math.h; exact for
+// |x| <= 2^19 pi/2).  The checker's comparison is false for a NaN product, which selects `even`.
+template <class R>
+__host__ __device__ RT_COLD V3<R> texture_value(const TexView<R>* tv, int tex, V3<R> p) {
+    const TexRec<R> t = tv->recs[tex];
+    const R s = t.scale;
+    if (t.type == TEX_CHECKER) {                                                      // textures.js:32-35
+        const R sines = (js_sin<R>(s * p.x) * js_sin<R>(s * p.y)) * js_sin<R>(s * p.z);
+        return sines < (R)0 ? mk(t.odd[0], t.odd[1], t.odd[2]) : mk(t.even[0], t.even[1], t.even[2]);
+    }
+    const int* perm = tv->perms + 512 * t.perm;
+    if (t.type == TEX_NOISE) {                                                        // :46-49
+        const R v = (R)0.5 * ((R)1 + perlin<R>(perm, p.x * s, p.y * s, p.z * s));
+        return mk(v, v, v);
+    }
+    if (t.type == TEX_MARBLE) {                                                       // :60-64
+        const R n = turbulence<R>(perm, p * s, 7);
+        const R m = (R)0.5 * ((R)1 + js_sin<R>(s * p.z + (R)10 * n)), w = (R)1 - m;
+        return mk<R>((R)0.9 * m + (R)0.6 * w, (R)0.8 * m + (R)0.4 * w, (R)0.7 * m + (R)0.3 * w);
+    }
+    const R k = s * (R)20;                                                            // wood :75-80
+    const R grain = perlin<R>(perm, p.x * k, p.y * k, p.z * k);
+    const R rings = js_sin<R>(s * sqrt(p.x * p.x + p.z * p.z) + grain * (R)10);
+    const R m = (R)0.5 * ((R)1 + rings), w = (R)1 - m;
+    return mk<R>((R)0.8 * m + (R)0.4 * w, (R)0.5 * m + (R)0.2 * w, (R)0.2 * m + (R)0.1 * w);
 }
 
 }  // namespace rt

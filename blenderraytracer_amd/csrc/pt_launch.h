@@ -123,6 +123,12 @@ template <class R>
 hipError_t launch_closest_hits(const SceneView<R>& sc, bool bvh, const double* rays, size_t n, double* t, int* kind,
                                int* idx, hipStream_t stream);
 
+// Texture.value of texture `tex` at n points (n x 3 doubles, device) -> rgb (n x 3 doubles, device):
+// rt_texture_values.  The scene must have textures (sc.tex), tex in [0, num_textures)
+template <class R>
+hipError_t launch_texture_values(const SceneView<R>& sc, int tex, const double* pts, size_t n, double* rgb,
+                                 hipStream_t stream);
+
 // default of rt_settings.sum_order = RT_SUM_POOL: the sample pool, unless RT_SAMPLE_POOL=0 is set in the
 // environment (A/B runs of the lane-per-pixel kernel)
 bool trace_uses_pool();

@@ -284,7 +284,17 @@ RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, 
             L = mk(T.x * m.c[0], T.y * m.c[1], T.z * m.c[2]);                 // emission
         } else {
             V3<R> nd, att;
-            if (scatter<R, (FEAT & F_TRIS) != 0 && FEAT != F_ALL>(m, h, unit, p, g, nd, att)) {
+            if (scatter<R, (FEAT & F_TRIS) != 0 && (FEAT & F_ALL) != F_ALL>(m, h, unit, p, g, nd, att)) {
+                // TexturedLambertian / TexturedMetal (materials.js:99-126) draw what their plain forms draw;
+                // only the attenuation differs: texture.value(u, v, rec.point).  (An absorbing TexturedMetal
+                // skips the texture: it has no draws and no side effects.)
+                if constexpr ((FEAT & F_TEX) != 0) {
+                    if (m.type <= 1) {
+                        const TexView<R>* tv = tex_view(sc);
+                        const int tex = tv->mat_tex[h.mat];
+                        if (tex >= 0) att = texture_value<R>(tv, tex, h.p);
+                    }
+                }
                 T = mk(T.x * att.x, T.y * att.y, T.z * att.z);
                 o = h.p;
                 d = nd;
@@ -334,8 +344,8 @@ RT_HD PixelResult trace_pixel(const SceneView<R>& sc, const ImageParams& im, int
         ++res.segments;
         V3<R> L;
         if (rec) T = mk<R>(1, 1, 1);           // then T = 1 * attenuation and L = 1 * X: exact
-        const bool done = shade_segment(sc, c, o, d, T, depth, g, L);
-        if constexpr (sizeof(R) == 8 && (ACC == ACC_BVH || ACC == ACC_BVH_STACK || ACC == ACC_BVH_STACK_LEAN))
+        const bool done = shade_segment<R, F_ALL | (feat_of<ACC>() & F_TEX)>(sc, c, o, d, T, depth, g, L);
+        if constexpr (sizeof(R) == 8 && (walk_of<ACC>() == ACC_BVH || walk_of<ACC>() == ACC_BVH_STACK || ACC == ACC_BVH_STACK_LEAN))
             skip_tri = !done && c.kind == HIT_TRI && leaves_tri_hull(sc, c.idx, o, d);
         const uint64_t t2 = RT_TICK();
         if (RT_PROFILE) res.cyc[1] += t2 - t1;

@@ -81,7 +81,7 @@ constexpr bool dyn_stack() { return sizeof(R) == 4 || (RT_F64_DYN_STACK != 0 && 
 // walks with a per-lane LDS stack (the ordered BVH walks)
 template <int ACC>
 constexpr bool uses_stack() {
-    return ACC == ACC_BVH_STACK || ACC == ACC_BVH_SPHERES || ACC == ACC_BVH_SPHERES_LDS || ACC == ACC_BVH_TRI_LDS ||
+    return walk_of<ACC>() == ACC_BVH_STACK || ACC == ACC_BVH_SPHERES || ACC == ACC_BVH_SPHERES_LDS || ACC == ACC_BVH_TRI_LDS ||
            ACC == ACC_BVH_STACK_LEAN;
 }
 
@@ -92,7 +92,8 @@ constexpr int waves_per_simd() {
     if constexpr (ACC == ACC_BVH_SPHERES) return sizeof(R) == 8 ? RT_SPHERES_WAVES_PER_SIMD : RT_SPHERES_WAVES_F32;
     if constexpr (ACC == ACC_BVH_SPHERES_LDS) return sizeof(R) == 8 ? RT_LDS_OCC_F64 : RT_LDS_OCC_F32;
     if constexpr (ACC == ACC_BVH_TRI_LDS) return sizeof(R) == 8 ? RT_BVH_WAVES_PER_SIMD : RT_BVH_WAVES_F32;
-    return ACC >= ACC_BVH ? (sizeof(R) == 8 ? RT_BVH_WAVES_PER_SIMD : RT_BVH_WAVES_F32) : RT_MIN_WAVES_PER_SIMD;
+    // (the textured kernels take their walks' occupancy: texture_value is out of line)
+    return walk_of<ACC>() >= ACC_BVH ? (sizeof(R) == 8 ? RT_BVH_WAVES_PER_SIMD : RT_BVH_WAVES_F32) : RT_MIN_WAVES_PER_SIMD;
 }
 
 // Per-wave reduction of the lanes' work counters into Counters::totals (one 64-bit atomic each).
@@ -100,7 +101,7 @@ template <int ACC>
 __device__ __forceinline__ void add_totals(const Counters& c, const PixelResult& r, const int lane) {
     if (!c.totals) return;
     const uint32_t parts[4] = {r.segments, r.work.nodes, r.work.spheres, r.work.tris};
-    for (int k = 0; k < (ACC >= ACC_BVH ? 4 : 1); ++k) {
+    for (int k = 0; k < (walk_of<ACC>() >= ACC_BVH ? 4 : 1); ++k) {
         unsigned long long v = parts[k];
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (lane == 0) atomicAdd(c.totals + k, v);
@@ -394,7 +395,7 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
             waiting = shade_segment<R, feat_of<ACC>()>(sc, c, o, d, T, depth, g, L);
             // the next segment leaves the triangle just hit away from every triangle: no triangle walk
             // (tri_exit_bound, pt_core.h; binary64 only)
-            if constexpr (sizeof(R) == 8 && (ACC == ACC_BVH || ACC == ACC_BVH_STACK || ACC == ACC_BVH_STACK_LEAN))
+            if constexpr (sizeof(R) == 8 && (walk_of<ACC>() == ACC_BVH || walk_of<ACC>() == ACC_BVH_STACK || ACC == ACC_BVH_STACK_LEAN))
                 skip_tri = !waiting && c.kind == HIT_TRI && leaves_tri_hull(sc, c.idx, o, d);
             if (RT_PROFILE) res.cyc[1] += RT_TICK() - t1;
             if (waiting) {
@@ -854,6 +855,11 @@ RT_ONEWAVE_INST(float, ACC_BVH_SPHERES)
 RT_ONEWAVE_INST(float, ACC_GRID)
 RT_ONEWAVE_INST(float, ACC_BVH_STACK_LEAN)
 RT_ONEWAVE_INST(float, ACC_BRUTE_LEAN)
+// scenes with procedural textures: World order and the general ordered walk (any mix of primitives)
+RT_ONEWAVE_INST(double, ACC_BRUTE_TEX)
+RT_ONEWAVE_INST(double, ACC_BVH_STACK_TEX)
+RT_ONEWAVE_INST(float, ACC_BRUTE_TEX)
+RT_ONEWAVE_INST(float, ACC_BVH_STACK_TEX)
 #undef RT_ONEWAVE_INST
 #else   // !RT_ONEWAVE_TU: the rest of the file
 
@@ -1204,7 +1210,10 @@ static hipError_t launch_lds_pool(const TraceArgs<R>& a, bool count, double* par
 // The lean kernels (feat_of, pt_core.h) serve launches whose scene has the sky gradient, the perspective
 // camera and supersampling AA, and the lean kernel's primitives: the grid's (ACC_GRID_LDS_LEAN) spheres
 // alone, the triangle BVH walk's (ACC_BVH_STACK_LEAN) and World order's (ACC_BRUTE_LEAN) no boxes (World
-// order: no triangles either).  RT_LEAN=0: never (A/B); 1 (default): all three; 2: the grid's only
+// order: no triangles either).  RT_LEAN=0: never (A/B); 1 (default): all three; 2: the grid's only.
+// A scene with procedural textures (SceneView::num_tex) never takes them: launch_* route it to the F_TEX
+// kernels (ACC_BRUTE_TEX / ACC_BVH_STACK_TEX: one-wave pool and lane-per-pixel forms only) before the
+// walk is chosen, so scenes without textures launch exactly the kernels they launched before.
 #ifndef RT_LEAN
 #define RT_LEAN 1
 #endif
@@ -1214,7 +1223,7 @@ static bool scene_lean(const SceneView<R>& sc, const ImageParams& im, int feat) 
         const char* e = getenv("RT_LEAN");
         return e ? atoi(e) : RT_LEAN;
     }();
-    if (v == 0 || (v == 2 && feat != 0)) return false;
+    if (v == 0 || (v == 2 && feat != 0) || sc.num_tex > 0) return false;   // (no lean kernel evaluates textures)
     return (sc.num_planes == 0 || (feat & F_PLANES)) && (sc.num_boxes == 0 || (feat & F_BOXES)) &&
            (sc.num_tri_nodes == 0 || (feat & F_TRIS)) && sc.background == 0 && !sc.cam_ortho && im.aa_mode == 0;
 }
@@ -1297,7 +1306,7 @@ static int bvh_walk_mode(const SceneView<R>& sc) {
 }
 
 template <class R>
-bool trace_walks_grid(const SceneView<R>& sc) { return bvh_walk_mode(sc) == ACC_GRID; }
+bool trace_walks_grid(const SceneView<R>& sc) { return sc.num_tex == 0 && bvh_walk_mode(sc) == ACC_GRID; }
 template bool trace_walks_grid<double>(const SceneView<double>&);
 template bool trace_walks_grid<float>(const SceneView<float>&);
 
@@ -1313,6 +1322,9 @@ hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Cou
     if (im.cw <= 0 || im.ch <= 0 || im.s_end <= im.s_begin) return hipSuccess;
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
+        return bvh ? launch_acc<R, ACC_BVH_STACK_TEX>(a, count, pool, stream)
+                   : launch_acc<R, ACC_BRUTE_TEX>(a, count, pool, stream);
     if (!bvh) return launch_acc<R, ACC_BRUTE>(a, count, pool, stream);
     const int mode = bvh_walk_mode(sc);
     if (mode == ACC_BVH) return launch_acc<R, ACC_BVH>(a, count, pool, stream);
@@ -1351,6 +1363,9 @@ hipError_t launch_trace_partials(const SceneView<R>& sc, const ImageParams& im, 
     if (!part || part_bytes < p.part_bytes) return hipErrorInvalidValue;
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
+        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, p, part, stream)
+                   : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, p, part, stream);
     if (!bvh) return launch_partials_acc<R, ACC_BRUTE>(a, count, p, part, stream);
     const int mode = bvh_walk_mode(sc);
     if (mode == ACC_BVH) return launch_partials_acc<R, ACC_BVH>(a, count, p, part, stream);
@@ -1389,6 +1404,9 @@ hipError_t launch_trace_batches(const SceneView<R>& sc, const ImageParams& im0, 
     const PoolPlan all{p.tiles, p.chunk, p.chunks * nb, (size_t)nb * p.part_bytes};
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
+        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, all, part, stream)
+                   : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, all, part, stream);
     if (!bvh) return launch_partials_acc<R, ACC_BRUTE>(a, count, all, part, stream);
     const int mode = bvh_walk_mode(sc);
     if (mode == ACC_BVH) return launch_partials_acc<R, ACC_BVH>(a, count, all, part, stream);
@@ -1427,6 +1445,9 @@ hipError_t launch_trace_bands(const SceneView<R>& sc, const ImageParams& im0, co
     im.band_chunks = p.chunks;
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
+        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, p, part, stream)
+                   : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, p, part, stream);
     if (!bvh) return launch_partials_acc<R, ACC_BRUTE>(a, count, p, part, stream);
     const int mode = bvh_walk_mode(sc);
     if (mode == ACC_BVH) return launch_partials_acc<R, ACC_BVH>(a, count, p, part, stream);
@@ -1544,7 +1565,11 @@ hipError_t launch_closest_hits(const SceneView<R>& sc, bool bvh, const double* r
                                int* idx, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 63) / 64));
-    const bool spheres = bvh && bvh_walk_mode(sc) == ACC_BVH_SPHERES;   // the walk the trace kernel runs
+    if (bvh && sc.num_tex > 0) {                                               // the walk the trace kernel runs
+        hipLaunchKernelGGL((closest_hits_kernel<R, ACC_BVH_STACK>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
+        return hipGetLastError();
+    }
+    const bool spheres = bvh && bvh_walk_mode(sc) == ACC_BVH_SPHERES;
     if (bvh && bvh_walk_mode(sc) == ACC_BVH_STACK && lds_tri_nodes(sc)) {
         SceneView<R> v = sc;
         v.tri_lds_nodes = lds_tri_nodes(sc);
@@ -1567,6 +1592,30 @@ template hipError_t launch_closest_hits<double>(const SceneView<double>&, bool, 
                                                 hipStream_t);
 template hipError_t launch_closest_hits<float>(const SceneView<float>&, bool, const double*, size_t, double*, int*, int*,
                                                hipStream_t);
+
+// ---- Texture.value at given points (rt_texture_values: texture_value, the trace kernels' function) ----
+template <class R>
+__global__ __launch_bounds__(64) void texture_values_kernel(const TexView<R>* __restrict__ tv, const int tex,
+                                                            const double* __restrict__ pts, const size_t n,
+                                                            double* __restrict__ rgb) {
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n) return;
+    const V3<R> v = texture_value<R>(tv, tex, mk<R>((R)pts[3 * r], (R)pts[3 * r + 1], (R)pts[3 * r + 2]));
+    rgb[3 * r] = (double)v.x;
+    rgb[3 * r + 1] = (double)v.y;
+    rgb[3 * r + 2] = (double)v.z;
+}
+
+template <class R>
+hipError_t launch_texture_values(const SceneView<R>& sc, int tex, const double* pts, size_t n, double* rgb,
+                                 hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (sc.num_tex <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((texture_values_kernel<R>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, tex_view(sc), tex, pts, n, rgb);
+    return hipGetLastError();
+}
+template hipError_t launch_texture_values<double>(const SceneView<double>&, int, const double*, size_t, double*, hipStream_t);
+template hipError_t launch_texture_values<float>(const SceneView<float>&, int, const double*, size_t, double*, hipStream_t);
 
 // ---- multi-device sample split: dst += src elementwise (the shards' sums / counters, in shard order) ----
 template <class T>

@@ -106,6 +106,10 @@ struct DeviceScene {
     DevBuf<Bvh2Node> sphere_wide, tri_wide;
     DevBuf<int> grid_cell;
     DevBuf<SphereLeaf<R>> grid_leaf;
+    // procedural textures (scene_textured only): records, tables, texture per material; the TexView over
+    // them is uploaded behind the world's table in `perm` (pt_core.h tex_view)
+    DevBuf<TexRec<R>> tex_recs;
+    DevBuf<int> tex_perms, mat_tex;
     SceneView<R> view{};
     void release() {
         runs.release(); spheres.release(); sphere_filter.release(); sphere_r.release(); sphere_inv_r.release(); planes.release(); boxes.release(); tris.release();
@@ -113,6 +117,7 @@ struct DeviceScene {
         plane_obj.release(); box_obj.release(); sphere_nodes.release(); tri_nodes.release(); bvh_sphere_leaf.release();
         bvh_tri_leaf.release(); tri_filter.release(); tri_exit.release(); big_sphere_leaf.release();
         sphere_wide.release(); tri_wide.release(); grid_cell.release(); grid_leaf.release();
+        tex_recs.release(); tex_perms.release(); mat_tex.release();
     }
 };
 
@@ -124,7 +129,13 @@ int build_device(DeviceScene<R>& ds, const HostScene& hs, const rt_scene_desc& d
 #define UP(buf, vec) if (e == hipSuccess) e = upload(ds.buf, vec)
     UP(runs, hs.runs); UP(spheres, rec.spheres); UP(sphere_filter, rec.sphere_filter); UP(sphere_r, rec.sphere_r); UP(sphere_inv_r, rec.sphere_inv_r); UP(planes, rec.planes);
     UP(boxes, rec.boxes); UP(tris, rec.tris); UP(sphere_mat, hs.sphere_mat); UP(plane_mat, hs.plane_mat);
-    UP(box_mat, hs.box_mat); UP(tri_mat, hs.tri_mat); UP(perm, rec.perm); UP(mats, rec.mats);
+    UP(box_mat, hs.box_mat); UP(tri_mat, hs.tri_mat); UP(mats, rec.mats);
+    const bool textured = !rec.tex_recs.empty();
+    if (textured) {          // the TexView over the uploaded arrays goes behind the world's table (tex_view)
+        UP(tex_recs, rec.tex_recs); UP(tex_perms, rec.tex_perms); UP(mat_tex, rec.mat_tex);
+        rec.set_tex_view(TexView<R>{ds.tex_recs.p, ds.tex_perms.p, ds.mat_tex.p, (int)rec.tex_recs.size(), d.num_texture_perms});
+    }
+    UP(perm, rec.perm);
     UP(plane_obj, hs.plane_obj); UP(box_obj, hs.box_obj); UP(sphere_nodes, hs.sphere_bvh); UP(tri_nodes, hs.tri_bvh);
     UP(bvh_sphere_leaf, rec.bvh_sphere_leaf); UP(bvh_tri_leaf, rec.bvh_tri_leaf); UP(tri_filter, rec.tri_filter); UP(big_sphere_leaf, rec.big_sphere_leaf); UP(sphere_wide, hs.sphere_wide); UP(tri_wide, hs.tri_wide);
     UP(grid_cell, hs.grid_cell); UP(grid_leaf, rec.grid_leaf); UP(tri_exit, hs.tri_exit);
@@ -264,8 +275,16 @@ struct DescCopy {
     std::vector<rt_object_desc> objects;
     std::vector<rt_material_desc> materials;
     std::vector<double> triangles;
+    std::vector<rt_texture_desc> textures;
+    std::vector<int32_t> material_texture, texture_perms;
     void set(const rt_scene_desc& src) {
         d = src;
+        textures.assign(src.textures, src.textures + std::max(0, src.num_textures));
+        if (src.material_texture) material_texture.assign(src.material_texture, src.material_texture + std::max(0, src.num_materials));
+        texture_perms.assign(src.texture_perms, src.texture_perms + 512 * (size_t)std::max(0, src.num_texture_perms));
+        d.textures = textures.data();
+        d.material_texture = src.material_texture ? material_texture.data() : nullptr;
+        d.texture_perms = texture_perms.data();
         objects.assign(src.objects, src.objects + std::max(0, src.num_objects));
         materials.assign(src.materials, src.materials + std::max(0, src.num_materials));
         triangles.assign(src.triangles, src.triangles + 12 * (size_t)std::max(0, src.num_triangles));
@@ -801,10 +820,13 @@ int rt_device_count(int* count) {
     return RT_OK;
 }
 
-int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
-    if (!desc || !out) return fail(RT_ERR_INVALID, "NULL argument");
+int rt_scene_create(const rt_scene_desc* caller_desc, int device, rt_scene** out) {
+    if (!caller_desc || !out) return fail(RT_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (desc->abi_version != RT_ABI_VERSION) return fail(RT_ERR_INVALID, "abi_version %d != %d", desc->abi_version, RT_ABI_VERSION);
+    rt_scene_desc filled;                 // the texture fields only where the caller says it filled them
+    if (!desc_as_filled(caller_desc, filled))
+        return fail(RT_ERR_INVALID, "abi_version %d != %d", caller_desc->abi_version, RT_ABI_VERSION);
+    const rt_scene_desc* desc = &filled;
     if (desc->num_objects < 0 || (desc->num_objects > 0 && !desc->objects)) return fail(RT_ERR_INVALID, "objects");
     if (desc->num_materials < 0 || (desc->num_materials > 0 && !desc->materials)) return fail(RT_ERR_INVALID, "materials");
     if (desc->num_triangles < 0 || (desc->num_triangles > 0 && !desc->triangles)) return fail(RT_ERR_INVALID, "triangles");
@@ -814,6 +836,10 @@ int rt_scene_create(const rt_scene_desc* desc, int device, rt_scene** out) {
     for (int i = 0; i < desc->num_materials; ++i)
         if (desc->materials[i].type < 0 || desc->materials[i].type > RT_MAT_EMISSIVE)
             return fail(RT_ERR_INVALID, "material %d: type %d", i, desc->materials[i].type);
+    {
+        std::string terr;                      // host-only checks first: a bad descriptor is RT_ERR_INVALID
+        if (!validate_textures(*desc, terr)) return fail(RT_ERR_INVALID, "%s", terr.c_str());   // with or without a device
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
     if (device < 0 || device >= ndev) return fail(RT_ERR_INVALID, "device %d of %d", device, ndev);
@@ -1730,6 +1756,31 @@ int rt_closest_hits(rt_scene* sc, int32_t precision, int32_t accel, const double
     if (e == hipSuccess) e = es;
     cleanup();
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_closest_hits: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_texture_values(rt_scene* sc, int32_t precision, int32_t texture, const double* points, size_t n, double* rgb) {
+    if (!sc || (n > 0 && (!points || !rgb))) return fail(RT_ERR_INVALID, "NULL argument");
+    if (precision != RT_PREC_F64 && precision != RT_PREC_F32) return fail(RT_ERR_INVALID, "precision %d", precision);
+    if (texture < 0 || texture >= sc->desc.d.num_textures)
+        return fail(RT_ERR_INVALID, "texture %d of %d", texture, sc->desc.d.num_textures);
+    if (!scene_textured(sc->desc.d)) return fail(RT_ERR_INVALID, "no material of the scene uses a texture");
+    if (n == 0) return RT_OK;
+    DeviceState& ds = sc->home;
+    HIP_TRY(hipSetDevice(ds.device));
+    DevBuf<double> d_pts, d_rgb;
+    hipError_t e = d_pts.ensure(3 * n);
+    if (e == hipSuccess) e = d_rgb.ensure(3 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pts.p, points, 3 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
+    if (e == hipSuccess)
+        e = precision == RT_PREC_F32 ? launch_texture_values<float>(ds.s32.view, texture, d_pts.p, n, d_rgb.p, ds.stream)
+                                     : launch_texture_values<double>(ds.s64.view, texture, d_pts.p, n, d_rgb.p, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rgb, d_rgb.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_pts.release();
+    d_rgb.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_texture_values: %s", hipGetErrorString(e));
     return RT_OK;
 }
 

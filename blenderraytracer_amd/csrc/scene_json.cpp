@@ -316,25 +316,80 @@ struct rt_json_scene {
     std::vector<rt_object_desc> objects;
     std::vector<rt_material_desc> materials;
     std::vector<double> triangles;
+    // the "texture" extension: one texture per textured material, the texture of each material (-1 none),
+    // 512 entries per noise-bearing texture
+    std::vector<rt_texture_desc> textures;
+    std::vector<int32_t> material_texture, texture_perms;
+    uint32_t seed = 0;
     rt_scene_desc desc{};
     int32_t width = 0, height = 0;
 };
 
 namespace {
 
-rt_material_desc make_material(const JVal* m) {   // scene-loader.js:143-173, materials.js constructors
+// PerlinNoise.p (noise.js:6-18) from the keyed stream select(pixel, sample): the world's table from
+// (0xFFFFFFFF, 0xFFFFFFFF), the k-th noise-bearing texture's from (0xFFFFFFFD, k)
+void keyed_permutation(uint32_t seed, int32_t* perm, uint32_t pixel = 0xFFFFFFFFu, uint32_t sample = 0xFFFFFFFFu) {
+    const uint32_t pkey = rt::pixel_key(rt::host_seed_mix(seed), pixel);
+    rt::Rng<double> g{rt::sample_key(pkey, sample), 0};
+    int p[256];
+    for (int i = 0; i < 256; ++i) p[i] = i;
+    for (int i = 255; i >= 0; --i) {
+        const int j = (int)std::floor(g.next() * (i + 1));
+        std::swap(p[i], p[j]);
+    }
+    for (int i = 0; i < 512; ++i) perm[i] = p[i & 255];
+}
+
+// The scene-JSON extension: an optional "texture" object inside a lambertian / metal
+// material, `type` one of createTexture's strings (ray-tracer.js:84-99); anything else is its default
+// branch, SolidColor(color): the plain material.  Returns false then; else fills t (and tp, the texture's
+// own permutation, for the noise-bearing kinds: the k-th of them in World.objects order)
+bool make_texture(const JVal* m, V color, uint32_t seed, uint32_t k, rt_texture_desc& t, std::vector<int32_t>& tp) {
+    const JVal* tj = m->get("texture");
+    if (!tj || tj->t != JVal::Obj) return false;
+    const JVal* ty = tj->get("type");
+    if (!ty || ty->t != JVal::Str) return false;
+    t = rt_texture_desc{};
+    t.perm = -1;
+    const JVal* sc = tj->get("scale");
+    if (ty->s == "checkerboard") {                  // CheckerTexture(color * 0.2, color, scale = 10)
+        t.type = RT_TEX_CHECKER;
+        t.scale = sc ? num(sc) : 10.0;
+        const V odd = tj->get("odd") ? parse_vec3(tj->get("odd")) : vmul(color, 0.2);
+        const V even = tj->get("even") ? parse_vec3(tj->get("even")) : color;
+        t.odd[0] = odd.x; t.odd[1] = odd.y; t.odd[2] = odd.z;
+        t.even[0] = even.x; t.even[1] = even.y; t.even[2] = even.z;
+        return true;
+    }
+    if (ty->s == "noise") t.type = RT_TEX_NOISE;
+    else if (ty->s == "marble") t.type = RT_TEX_MARBLE;
+    else if (ty->s == "wood") t.type = RT_TEX_WOOD;
+    else return false;
+    t.scale = sc ? num(sc) : 1.0;
+    tp.resize(512);
+    keyed_permutation(seed, tp.data(), 0xFFFFFFFDu, k);
+    return true;
+}
+
+// has_tex: the material is TexturedLambertian / TexturedMetal with texture `tex` (tp: its permutation)
+rt_material_desc make_material(const JVal* m, uint32_t seed = 0, uint32_t k = 0, bool* has_tex = nullptr,
+                               rt_texture_desc* tex = nullptr, std::vector<int32_t>* tp = nullptr) {   // scene-loader.js:143-173
     rt_material_desc d{};
     d.type = RT_MAT_LAMBERTIAN;
     d.albedo[0] = d.albedo[1] = d.albedo[2] = 0.8;
+    if (has_tex) *has_tex = false;
     if (!truthy(m) || !truthy(m->get("type"))) return d;
     const std::string t = type_of(m->get("type"), "material");
     if (t == "lambertian") {
         const V c = parse_vec3(m->get("color"));
         d.albedo[0] = c.x; d.albedo[1] = c.y; d.albedo[2] = c.z;
+        if (has_tex && (*has_tex = make_texture(m, c, seed, k, *tex, *tp))) d.albedo[0] = d.albedo[1] = d.albedo[2] = 0;
     } else if (t == "metal") {
         const V c = parse_vec3(m->get("color"));
         d.type = RT_MAT_METAL;
         d.albedo[0] = c.x; d.albedo[1] = c.y; d.albedo[2] = c.z;
+        if (has_tex && (*has_tex = make_texture(m, c, seed, k, *tex, *tp))) d.albedo[0] = d.albedo[1] = d.albedo[2] = 0;
         const JVal* r = m->get("roughness");
         const double rough = r ? num(r) : 0.0;
         d.roughness = rough != rough ? NAN : (rough < 1 ? rough : 1.0);   // Math.min(roughness, 1)
@@ -369,8 +424,11 @@ void create_object(rt_json_scene& s, const JVal& o) {      // scene-loader.js:90
     if (!truthy(o.get("type"))) return;                    // "Object has no type" -> skipped
     const JVal* mj = o.get("material");
     rt_material_desc mat;
+    bool has_tex = false;
+    rt_texture_desc tex{};
+    std::vector<int32_t> tperm;
     if (truthy(mj)) {
-        mat = make_material(mj);
+        mat = make_material(mj, s.seed, (uint32_t)(s.texture_perms.size() / 512), &has_tex, &tex, &tperm);
     } else {
         mat = rt_material_desc{};
         mat.type = RT_MAT_LAMBERTIAN;
@@ -425,6 +483,14 @@ void create_object(rt_json_scene& s, const JVal& o) {      // scene-loader.js:90
     }
     d.material = (int32_t)s.materials.size();
     s.materials.push_back(mat);
+    s.material_texture.push_back(has_tex ? (int32_t)s.textures.size() : -1);
+    if (has_tex) {                                         // (an object that was not added left no texture)
+        if (!tperm.empty()) {
+            tex.perm = (int32_t)(s.texture_perms.size() / 512);
+            s.texture_perms.insert(s.texture_perms.end(), tperm.begin(), tperm.end());
+        }
+        s.textures.push_back(tex);
+    }
     s.objects.push_back(d);
 }
 
@@ -461,18 +527,6 @@ Camera setup_camera(const Camera& c, int32_t w, int32_t h) {   // ray-tracer.js:
                        c.perspective ? "perspective" : (c.orthographic ? "orthographic" : "other"));
 }
 
-void keyed_permutation(uint32_t seed, int32_t* perm) {     // noise.js:6-18 from the keyed perm stream
-    const uint32_t pkey = rt::pixel_key(rt::host_seed_mix(seed), 0xFFFFFFFFu);
-    rt::Rng<double> g{rt::sample_key(pkey, 0xFFFFFFFFu), 0};
-    int p[256];
-    for (int i = 0; i < 256; ++i) p[i] = i;
-    for (int i = 255; i >= 0; --i) {
-        const int j = (int)std::floor(g.next() * (i + 1));
-        std::swap(p[i], p[j]);
-    }
-    for (int i = 0; i < 512; ++i) perm[i] = p[i & 255];
-}
-
 }  // namespace
 
 extern "C" {
@@ -492,6 +546,7 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
     try {
         s->width = width;
         s->height = height;
+        s->seed = seed;
         const JVal* cam = root.get("camera");
         bool resized = false;
         if (truthy(cam) && truthy(cam->get("resolution"))) {   // scene-loader.js:24-33
@@ -505,6 +560,7 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
         }
         rt_scene_desc& d = s->desc;
         d.abi_version = RT_ABI_VERSION;
+        d.extensions = RT_DESC_TEXTURES;                 // the texture fields are filled below
         d.background = RT_BG_GRADIENT;                       // world.js:12
         d.sky_intensity = 1.0;
         d.solid_color[0] = d.solid_color[1] = d.solid_color[2] = 0.1;
@@ -554,6 +610,11 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
         d.materials = s->materials.data();
         d.num_triangles = (int32_t)(s->triangles.size() / 12);
         d.triangles = s->triangles.data();
+        d.num_textures = (int32_t)s->textures.size();
+        d.textures = s->textures.data();
+        d.material_texture = s->material_texture.data();
+        d.num_texture_perms = (int32_t)(s->texture_perms.size() / 512);
+        d.texture_perms = s->texture_perms.data();
     } catch (const LoadError& e) {
         return rt::set_error(RT_ERR_INVALID, e.msg.c_str());
     } catch (const std::bad_alloc&) {

@@ -123,6 +123,53 @@ inline bool pack_host(const rt_scene_desc& d, HostScene& hs, std::string& err) {
     return true;
 }
 
+// The descriptor as far as its caller filled it (rt_hip.h rt_scene_desc.extensions): a copy whose texture
+// fields are the caller's when extensions == RT_DESC_TEXTURES and zero (no textures) otherwise — nothing
+// behind `perm` is read then, so a caller built against the shorter struct stays valid.  false: another
+// abi_version
+inline bool desc_as_filled(const rt_scene_desc* d, rt_scene_desc& out) {
+    if (d->abi_version != RT_ABI_VERSION) return false;
+    memset(&out, 0, sizeof out);
+    memcpy(&out, d, d->extensions == RT_DESC_TEXTURES ? sizeof out : offsetof(rt_scene_desc, num_textures));
+    return true;
+}
+
+// The texture part of the descriptor (extensions == RT_DESC_TEXTURES), checked on the host before anything is uploaded: indices in
+// range, textures on Lambertian / Metal only, permutation entries in 0..255, finite scales.
+inline bool validate_textures(const rt_scene_desc& d, std::string& err) {
+    char buf[256];
+    auto bad = [&](const char* fmt, int a, int b) { snprintf(buf, sizeof buf, fmt, a, b); err = buf; return false; };
+    if (d.num_textures < 0 || (d.num_textures > 0 && !d.textures)) return bad("textures (%d)", d.num_textures, 0);
+    if (d.num_texture_perms < 0 || (d.num_texture_perms > 0 && !d.texture_perms))
+        return bad("texture_perms (%d)", d.num_texture_perms, 0);
+    if (d.num_textures > 0 && d.num_materials > 0 && !d.material_texture) return bad("material_texture is NULL with %d textures", d.num_textures, 0);
+    for (int i = 0; i < d.num_textures; ++i) {
+        const rt_texture_desc& t = d.textures[i];
+        if (t.type < RT_TEX_CHECKER || t.type > RT_TEX_WOOD) return bad("texture %d: type %d", i, t.type);
+        if (!std::isfinite(t.scale)) return bad("texture %d: scale is not finite", i, 0);
+        if (t.type == RT_TEX_CHECKER ? t.perm != -1 : (t.perm < 0 || t.perm >= d.num_texture_perms))
+            return bad("texture %d: perm index %d out of range", i, t.perm);
+    }
+    for (long long i = 0; i < 512LL * d.num_texture_perms; ++i)
+        if (d.texture_perms[i] < 0 || d.texture_perms[i] > 255)
+            return bad("texture_perms[%d] = %d", (int)i, d.texture_perms[i]);
+    if (d.material_texture)
+        for (int i = 0; i < d.num_materials; ++i) {
+            const int t = d.material_texture[i];
+            if (t < -1 || t >= d.num_textures) return bad("material %d: texture index %d out of range", i, t);
+            if (t >= 0 && d.materials[i].type != RT_MAT_LAMBERTIAN && d.materials[i].type != RT_MAT_METAL)
+                return bad("material %d: texture on material type %d (Lambertian / Metal only)", i, d.materials[i].type);
+        }
+    return true;
+}
+// a material of the scene takes its attenuation from a texture (the launch then takes the F_TEX kernels)
+inline bool scene_textured(const rt_scene_desc& d) {
+    if (d.num_textures <= 0 || !d.material_texture) return false;
+    for (int i = 0; i < d.num_materials; ++i)
+        if (d.material_texture[i] >= 0) return true;
+    return false;
+}
+
 // ---- BVH (binned SAH, preorder with skip links) over spheres and over triangles ---------------------
 // Node bounds are inflated on every axis by 2^-19 max|bound| (the node's largest coordinate) and
 // rounded outward to binary32, so that the binary32 slab test of pt_core.h (bvh_node_hit) is
@@ -655,6 +702,16 @@ struct HostRecords {
     std::vector<TriRec<R>> tris;
     std::vector<MatRec<R>> mats;
     std::vector<int> perm;
+    // procedural textures (empty unless scene_textured): records, 512-int tables, texture per material.  The
+    // TexView over them (host pointers: host_view; device pointers: rt_capi.cpp) is appended to `perm`
+    // (set_tex_view), where tex_view(SceneView) reads it
+    std::vector<TexRec<R>> tex_recs;
+    std::vector<int> tex_perms, mat_tex;
+    void set_tex_view(const TexView<R>& tv) {
+        static_assert(sizeof(TexView<R>) % sizeof(int) == 0, "TexView in ints");
+        perm.resize(kTexViewAt + sizeof(TexView<R>) / sizeof(int));
+        memcpy(perm.data() + kTexViewAt, &tv, sizeof tv);
+    }
     // BVH leaf-order records (bvh_sphere_leaf[k] describes spheres[bvh_sphere_leaf[k].id], same for
     // triangles)
     std::vector<SphereLeaf<R>> bvh_sphere_leaf;
@@ -721,6 +778,20 @@ void make_records(const HostScene& hs, const rt_scene_desc& d, HostRecords<R>& o
         out.mats[i] = r;
     }
     out.perm.assign(d.perm, d.perm + 512);
+    if (scene_textured(d)) {
+        out.tex_recs.resize(d.num_textures);
+        for (int i = 0; i < d.num_textures; ++i) {
+            const rt_texture_desc& t = d.textures[i];
+            TexRec<R> r{};
+            r.type = t.type;
+            r.perm = t.perm;
+            r.scale = (R)t.scale;
+            for (int k = 0; k < 3; ++k) { r.odd[k] = (R)t.odd[k]; r.even[k] = (R)t.even[k]; }
+            out.tex_recs[i] = r;
+        }
+        out.tex_perms.assign(d.texture_perms, d.texture_perms + 512 * (size_t)d.num_texture_perms);
+        out.mat_tex.assign(d.material_texture, d.material_texture + d.num_materials);
+    }
     auto leaf = [&](int id) {
         SphereLeaf<R> L{};
         if constexpr (sizeof(R) == 8) L.f = out.sphere_filter[id];
@@ -749,6 +820,7 @@ void fill_view_constants(SceneView<R>& v, const HostScene& hs, const rt_scene_de
     v.num_prims = hs.num_prims;
     v.num_planes = (int)hs.plane_mat.size();
     v.num_mats = d.num_materials;
+    v.num_tex = scene_textured(d) ? d.num_textures : 0;
     v.num_boxes = (int)hs.box_mat.size();
     v.num_sphere_nodes = (int)hs.sphere_bvh.size();
     v.num_tri_nodes = (int)hs.tri_bvh.size();
@@ -817,6 +889,11 @@ inline SceneView<double> host_view(const HostScene& hs, const rt_scene_desc& d, 
     v.big_spheres = rec.big_sphere_leaf.data();
     v.sphere_wide = hs.sphere_wide.data(); v.tri_wide = hs.tri_wide.data();
     v.grid_cell = hs.grid_cell.data(); v.grid_leaf = rec.grid_leaf.data();
+    if (!rec.tex_recs.empty()) {
+        rec.set_tex_view(TexView<double>{rec.tex_recs.data(), rec.tex_perms.data(), rec.mat_tex.data(),
+                                         (int)rec.tex_recs.size(), d.num_texture_perms});
+        v.perm = rec.perm.data();
+    }
     fill_view_constants(v, hs, d);
     return v;
 }

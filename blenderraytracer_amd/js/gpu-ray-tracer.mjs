@@ -13,7 +13,7 @@ import { createRequire } from 'module';
 import path from 'path';
 import { fileURLToPath } from 'url';
 import { packScene } from './pack.mjs';
-import { Vec3, BG, defaultScene, loadFromJSON, setupCamera, permutation } from './scene-model.mjs';
+import { Vec3, BG, defaultScene, loadFromJSON, setupCamera, permutation, texturePermutation } from './scene-model.mjs';
 
 const HERE = path.dirname(fileURLToPath(import.meta.url));
 let native = null;
@@ -87,7 +87,7 @@ const isCancelled = () => typeof window !== 'undefined' && window && window.rend
 const bytesOf = (a) => Buffer.from(a.buffer, a.byteOffset, a.byteLength);
 function samePacked(a, b) {
     if (!a || !b) return false;
-    for (const k of ['objects', 'materials', 'triangles', 'camera', 'solidColor', 'perm'])
+    for (const k of ['objects', 'materials', 'triangles', 'camera', 'solidColor', 'perm', 'textures', 'materialTexture', 'texturePerms'])
         if (!bytesOf(a[k]).equals(bytesOf(b[k]))) return false;
     return a.cameraType === b.cameraType && a.background === b.background && Object.is(a.skyIntensity, b.skyIntensity);
 }
@@ -209,7 +209,8 @@ export class GpuRayTracer {
 
     loadFromJSON(json) {                                             // ray-tracer.js:305-334
         try {
-            const r = loadFromJSON(json, this.width, this.height, permutation(this.opts.seed || 0));
+            const seed = this.opts.seed || 0;
+            const r = loadFromJSON(json, this.width, this.height, permutation(seed), (k) => texturePermutation(seed, k));
             this.world = r.world;
             if (r.camera) this.camera = r.camera;
             if (r.newDimensions) this.resizeCanvas(r.newDimensions.width, r.newDimensions.height);

@@ -38,9 +38,9 @@ export class KeyedStream {
 }
 
 // Perlin permutation p[512] exactly as js/noise.js:6-18 shuffles it, drawing from the perm stream.
-export function permutation(seed) {
+export function permutation(seed, pixel = PERM_STREAM, sample = PERM_STREAM) {
     const st = new KeyedStream(seed);
-    st.select(PERM_STREAM, PERM_STREAM);
+    st.select(pixel, sample);
     const p = [];
     for (let i = 0; i < 256; i++) p[i] = i;
     for (let i = 255; i >= 0; i--) {
@@ -50,3 +50,9 @@ export function permutation(seed) {
     for (let i = 0; i < 256; i++) p[256 + i] = p[i];
     return p;
 }
+
+// PerlinNoise.p of the k-th noise-bearing texture (NoiseTexture / MarbleTexture / WoodTexture own one each,
+// textures.js:43,57,72), k counted in order of first appearance walking World.objects: the same shuffle
+// from the keyed stream select(0xFFFFFFFD, k).  World.cloudNoise keeps (0xFFFFFFFF, 0xFFFFFFFF).
+export const TEXTURE_PERM_STREAM = 0xFFFFFFFD;
+export function texturePermutation(seed, k) { return permutation(seed, TEXTURE_PERM_STREAM, k); }

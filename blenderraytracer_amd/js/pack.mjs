@@ -9,10 +9,43 @@ const MAT = { lambertian: 0, metal: 1, dielectric: 2, emissive: 3 };
 export const BG_CODE = { gradient: 0, solid: 1, hdri: 2, procedural_sky: 3, nan: 4 };
 export const OBJECT_BYTES = 64;
 export const MATERIAL_BYTES = 72;
+export const TEXTURE_BYTES = 64;
+export const TEX = { checker: 0, noise: 1, marble: 2, wood: 3 };
 
-function materialRecord(m) {
+// A texture object of TexturedLambertian / TexturedMetal (materials.js:99-126), duck-typed on the reference's
+// fields (textures.js:9-81): CheckerTexture has odd / even / scale; the noise-bearing ones have scale and
+// noise.p and are told apart by class name (the reference's classes and the twins of scene-model.mjs carry
+// the same names; a `kind` member overrides it for other hosts); SolidColor has color; anything else that
+// has value() but none of these is the base Texture (white).  Returns {solid: [r, g, b]} for the two
+// constants — the caller lowers them to the plain material — or the texture record.
+function textureRecord(t) {
+    if (t == null) throw new Error('textured material without texture');
+    const v = (c) => [c.x, c.y, c.z];
+    if (t.odd !== undefined && t.even !== undefined) return { type: TEX.checker, scale: t.scale, odd: v(t.odd), even: v(t.even) };
+    if (t.noise !== undefined && t.noise !== null && t.noise.p !== undefined) {
+        const name = String(t.kind || (t.constructor && t.constructor.name) || '').toLowerCase();
+        const type = name.indexOf('marble') >= 0 ? TEX.marble : name.indexOf('wood') >= 0 ? TEX.wood
+            : name.indexOf('noise') >= 0 ? TEX.noise : -1;
+        if (type < 0) throw new Error('unsupported noise texture (class name / kind must name noise, marble or wood)');
+        if (t.noise.p.length !== 512) throw new Error('texture.noise.p must have 512 entries');
+        return { type, scale: t.scale, p: t.noise.p };
+    }
+    if (t.color !== undefined) return { solid: v(t.color) };                 // SolidColor
+    if (typeof t.value === 'function' || Object.keys(t).length === 0) return { solid: [1, 1, 1] };   // base Texture
+    throw new Error('unsupported texture');
+}
+
+// tex(texture) -> index of the texture's record (textures deduplicated by object identity), or {solid}
+function materialRecord(m, tex) {
     if (m == null) throw new Error('object without material');
-    if (m.texture !== undefined) throw new Error('textured materials are not reachable from render() (SURVEY §0) and not supported');
+    if (m.texture !== undefined) {
+        // TexturedMetal has roughness, TexturedLambertian does not; both draw what their plain forms draw
+        const metal = m.roughness !== undefined;
+        const t = tex(m.texture);
+        const base = metal ? { type: MAT.metal, roughness: m.roughness } : { type: MAT.lambertian };
+        // SolidColor / base Texture: exactly Lambertian(c) / Metal(c, roughness)
+        return t.solid ? { ...base, albedo: t.solid } : { ...base, albedo: [0, 0, 0], texture: t.index };
+    }
     if (m.refractionIndex !== undefined) return { type: MAT.dielectric, ior: m.refractionIndex };
     if (m.intensity !== undefined && m.color !== undefined) {
         // materials.js:95: emitted = color.mul(intensity), evaluated in double exactly as the reference does
@@ -60,8 +93,21 @@ function triangleRecord(t, out, k) {
 export function packScene(world, camera) {
     const mats = [];
     const matIndex = new Map();
+    const texs = [], texIndex = new Map(), texPerms = [];
+    const texOf = (t) => {
+        if (!texIndex.has(t)) {
+            const r = textureRecord(t);
+            if (!r.solid) {
+                r.index = texs.length;
+                if (r.p) { r.perm = texPerms.length; texPerms.push(r.p); } else r.perm = -1;
+                texs.push(r);
+            }
+            texIndex.set(t, r);
+        }
+        return texIndex.get(t);
+    };
     const matOf = (m) => {
-        if (!matIndex.has(m)) { matIndex.set(m, mats.length); mats.push(materialRecord(m)); }
+        if (!matIndex.has(m)) { matIndex.set(m, mats.length); mats.push(materialRecord(m, texOf)); }
         return matIndex.get(m);
     };
     let ntri = 0;
@@ -117,6 +163,18 @@ export function packScene(world, camera) {
         mf[b + 5] = m.ior || 0;
         mf[b + 6] = em[0]; mf[b + 7] = em[1]; mf[b + 8] = em[2];
     }
+    // rt_texture_desc records, the texture of each material (-1: none) and the noise-bearing textures' tables
+    const textures = new ArrayBuffer(TEXTURE_BYTES * texs.length);
+    const ti = new Int32Array(textures), tf = new Float64Array(textures);
+    texs.forEach((t, i) => {
+        const b = i * (TEXTURE_BYTES / 8);
+        ti[2 * b] = t.type; ti[2 * b + 1] = t.perm;
+        tf[b + 1] = t.scale;
+        if (t.odd) { tf.set(t.odd, b + 2); tf.set(t.even, b + 5); }
+    });
+    const materialTexture = Int32Array.from(mats, (m) => (m.texture !== undefined ? m.texture : -1));
+    const texturePerms = new Int32Array(512 * texPerms.length);
+    texPerms.forEach((p, i) => texturePerms.set(p, 512 * i));
     const c = camera;
     const cam = new Float64Array(22);
     [c.origin, c.lowerLeftCorner, c.horizontal, c.vertical, c.u, c.v, c.w].forEach((v, j) => cam.set([v.x, v.y, v.z], 3 * j));
@@ -132,5 +190,8 @@ export function packScene(world, camera) {
         skyIntensity: world.skyIntensity,
         solidColor: new Float64Array(bg.solid),
         perm: Int32Array.from(world.cloudNoise.p),
+        textures: new Uint8Array(textures),
+        materialTexture,
+        texturePerms,
     };
 }

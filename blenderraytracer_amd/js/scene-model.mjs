@@ -4,10 +4,11 @@
 //   Vec3                       js/math.js:6-32
 //   Camera constructor         js/camera.js:8-36
 //   Plane / Triangle / Mesh    js/geometry.js:50-53, 140-146, 193-237
-//   materials                  js/materials.js:14-96
+//   materials                  js/materials.js:14-126
+//   textures                   js/textures.js:9-81 (fields only: the values are computed on the GPU)
 //   World + backgrounds        js/world.js:8-16 (background kinds are tagged, see backgroundKind)
 //   SceneLoader.loadFromJSON   js/scene-loader.js:20-284
-import { permutation } from './keyed-rng.mjs';
+import { permutation, texturePermutation } from './keyed-rng.mjs';
 
 export class Vec3 {
     constructor(x = 0, y = 0, z = 0) { this.x = x; this.y = y; this.z = z; }
@@ -57,6 +58,17 @@ export class Emissive {
     emitted() { return this.color.mul(this.intensity); }
 }
 
+// textures: the reference classes' member names and constructor defaults (textures.js:14-81).  The
+// noise-bearing ones own a PerlinNoise whose table the reference shuffles with Math.random; here the
+// permutation (512 entries, keyed-rng.mjs texturePermutation) is an argument.
+export class SolidColor { constructor(color) { this.color = color; } }
+export class CheckerTexture { constructor(odd, even, scale = 10) { this.odd = odd; this.even = even; this.scale = scale; } }
+export class NoiseTexture { constructor(perm, scale = 1) { this.scale = scale; this.noise = { p: perm }; } }
+export class MarbleTexture { constructor(perm, scale = 1) { this.scale = scale; this.noise = { p: perm }; } }
+export class WoodTexture { constructor(perm, scale = 1) { this.scale = scale; this.noise = { p: perm }; } }
+export class TexturedLambertian { constructor(texture) { this.texture = texture; } }
+export class TexturedMetal { constructor(texture, roughness = 0) { this.texture = texture; this.roughness = Math.min(roughness, 1); } }
+
 // geometry: same fields as the reference classes
 export class Sphere { constructor(center, radius, material) { this.center = center; this.radius = radius; this.material = material; } }
 export class Plane { constructor(point, normal, material) { this.point = point; this.normal = normal.normalize(); this.material = material; } }
@@ -97,20 +109,53 @@ export class World {
 
 const parseVec3 = (a) => (Array.isArray(a) && a.length >= 3 ? new Vec3(a[0], a[1], a[2]) : new Vec3(0, 0, 0));
 
-function createMaterial(m) {
+// The scene-JSON extension (INTEGRATION.md): an optional "texture" object inside a lambertian / metal
+// material, `type` one of createTexture's strings (ray-tracer.js:84-99); anything else is its default
+// branch, SolidColor(color), i.e. the plain material (null here).  tp: { next, perm(k) } hands the k-th
+// noise-bearing texture its permutation.
+function createTexture(m, color, tp) {
+    const t = m.texture;
+    if (!t || typeof t !== 'object' || Array.isArray(t) || !tp) return null;
+    const scale = (d) => (t.scale !== undefined ? t.scale : d);
+    switch (t.type) {
+        case 'checkerboard':                                     // CheckerTexture(color * 0.2, color, scale = 10)
+            return new CheckerTexture(t.odd !== undefined ? parseVec3(t.odd) : color.mul(0.2),
+                t.even !== undefined ? parseVec3(t.even) : color, scale(10));
+        case 'noise': return new NoiseTexture(tp.perm(tp.next++), scale(1));
+        case 'marble': return new MarbleTexture(tp.perm(tp.next++), scale(1));
+        case 'wood': return new WoodTexture(tp.perm(tp.next++), scale(1));
+        default: return null;
+    }
+}
+
+function createMaterial(m, tp) {
     if (!m || !m.type) return new Lambertian(new Vec3(0.8, 0.8, 0.8));
     switch (m.type.toLowerCase()) {
-        case 'lambertian': return new Lambertian(parseVec3(m.color));
-        case 'metal': return new Metal(parseVec3(m.color), m.roughness !== undefined ? m.roughness : 0.0);
+        case 'lambertian': {
+            const color = parseVec3(m.color), tex = createTexture(m, color, tp);
+            return tex ? new TexturedLambertian(tex) : new Lambertian(color);
+        }
+        case 'metal': {
+            const color = parseVec3(m.color), tex = createTexture(m, color, tp);
+            const roughness = m.roughness !== undefined ? m.roughness : 0.0;
+            return tex ? new TexturedMetal(tex, roughness) : new Metal(color, roughness);
+        }
         case 'dielectric': return new Dielectric(m.ior !== undefined ? m.ior : 1.5);
         case 'emissive': return new Emissive(parseVec3(m.color), m.intensity !== undefined ? m.intensity : 1.0);
         default: return new Lambertian(new Vec3(0.8, 0.8, 0.8));
     }
 }
 
-function createObject(o) {
+function createObject(o, tp) {
+    const k0 = tp ? tp.next : 0;
+    const obj = createObjectOf(o, tp);
+    if (!obj && tp) tp.next = k0;                // no object: its texture does not count (k follows World.objects)
+    return obj;
+}
+
+function createObjectOf(o, tp) {
     if (!o.type) return null;
-    const material = createMaterial(o.material || { type: 'lambertian', color: [0.8, 0.8, 0.8] });
+    const material = createMaterial(o.material || { type: 'lambertian', color: [0.8, 0.8, 0.8] }, tp);
     switch (o.type.toLowerCase()) {
         case 'sphere': return new Sphere(parseVec3(o.center), o.radius || 1.0, material);
         case 'plane': return new Plane(parseVec3(o.point), parseVec3(o.normal), material);
@@ -140,7 +185,8 @@ export function createCamera(cam, aspect) {
 
 // SceneLoader.loadFromJSON: perm = World.cloudNoise.p for the new World (reference: Math.random
 // shuffle at construction; here passed in so that it can come from the keyed RNG).
-export function loadFromJSON(json, width, height, perm) {
+// texturePerm(k): the permutation of the k-th noise-bearing texture (scenes with "texture" entries).
+export function loadFromJSON(json, width, height, perm, texturePerm) {
     let newDimensions = null;
     if (json.camera && json.camera.resolution) {
         newDimensions = { width: json.camera.resolution[0], height: json.camera.resolution[1] };
@@ -153,7 +199,8 @@ export function loadFromJSON(json, width, height, perm) {
         world.backgroundKind = t === 'solid' || t === 'hdri' ? BG.nan : t === 'procedural_sky' ? BG.procedural_sky : BG.gradient;
         if (json.background.intensity !== undefined) world.skyIntensity = json.background.intensity;
     }
-    if (Array.isArray(json.objects)) for (const o of json.objects) { const obj = createObject(o); if (obj) world.add(obj); }
+    const tp = texturePerm ? { next: 0, perm: texturePerm } : null;
+    if (Array.isArray(json.objects)) for (const o of json.objects) { const obj = createObject(o, tp); if (obj) world.add(obj); }
     // lights (scene-loader.js:69-76) are parsed but never rendered; _createLight calls
     // lightData.type.toLowerCase() (:187), which throws for a truthy non-string type: the load fails
     if (json.lights && Array.isArray(json.lights))
@@ -181,4 +228,4 @@ export function setupCamera(camera, width, height) {
         camera.focusDist || 10.0, camera.type || 'perspective');
 }
 
-export { permutation };
+export { permutation, texturePermutation };

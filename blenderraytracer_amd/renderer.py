@@ -12,7 +12,8 @@ import numpy as np
 
 from . import capi
 from .jsmath import js_exp
-from .scene import PackedScene, default_scene, load_from_json, setup_camera, keyed_permutation, js_or, truthy
+from .scene import (PackedScene, default_scene, load_from_json, setup_camera, keyed_permutation,
+                    keyed_texture_permutation, js_or, truthy)
 
 
 def settings_struct(width, height, samples, max_bounces, anti_aliasing, tone_mapping, exposure, gamma, seed,
@@ -74,7 +75,8 @@ class GpuRayTracer:
     # ---- RayTracer API --------------------------------------------------------------------------
     def load_from_json(self, data):
         try:
-            world, camera, dims = load_from_json(data, self.width, self.height, keyed_permutation(self.seed))
+            world, camera, dims = load_from_json(data, self.width, self.height, keyed_permutation(self.seed),
+                                                 keyed_texture_permutation(self.seed))
         except Exception:   # ray-tracer.js:330-333: errors -> false
             return False
         self.world = world

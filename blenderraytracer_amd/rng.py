@@ -44,12 +44,22 @@ class KeyedStream:
         return r
 
 
-def permutation(seed):
+TEXTURE_PERM_STREAM = 0xFFFFFFFD
+
+
+def permutation(seed, pixel=PERM_STREAM, sample=PERM_STREAM):
     """PerlinNoise.p exactly as js/noise.js:6-18 shuffles it, from the keyed perm stream."""
     st = KeyedStream(seed)
-    st.select(PERM_STREAM, PERM_STREAM)
+    st.select(pixel, sample)
     p = list(range(256))
     for i in range(255, -1, -1):
         j = math.floor(st.next() * (i + 1))
         p[i], p[j] = p[j], p[i]
     return p + p
+
+
+def texture_permutation(seed, k):
+    """PerlinNoise.p of the k-th noise-bearing texture (NoiseTexture / MarbleTexture / WoodTexture, counted in
+    order of first appearance walking World.objects): the same shuffle from the keyed stream
+    select(0xFFFFFFFD, k).  World.cloudNoise keeps (0xFFFFFFFF, 0xFFFFFFFF)."""
+    return permutation(seed, TEXTURE_PERM_STREAM, k)

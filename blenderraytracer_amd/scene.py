@@ -18,7 +18,7 @@ import numpy as np
 
 from . import capi
 from .jsmath import js_tan
-from .rng import permutation
+from .rng import permutation, texture_permutation
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES_DIR = os.path.join(REPO, "scenes")
@@ -108,15 +108,44 @@ class Camera:
 
 
 # ---- materials / objects ------------------------------------------------------------------------
-def _material(m):  # scene-loader.js:143-173 + materials.js constructors
+_TEXTURE_TYPES = {"checkerboard": "checker", "noise": "noise", "marble": "marble", "wood": "wood"}
+
+
+def _texture(m, color, world):
+    """The scene-JSON extension: an optional "texture" object inside a lambertian / metal
+    material, `type` one of createTexture's strings (ray-tracer.js:84-99); anything else is its default
+    branch, SolidColor(color), which is the plain material (None here).  Returns ("checker", scale, odd, even)
+    or (kind, scale, k): k the index of the texture's own permutation in world.texture_perms."""
+    t = m.get("texture")
+    if not isinstance(t, dict) or world is None:
+        return None
+    kind = _TEXTURE_TYPES.get(t.get("type")) if isinstance(t.get("type"), str) else None
+    if kind is None:
+        return None
+    if kind == "checker":                          # CheckerTexture(color * 0.2, color, scale = 10), ray-tracer.js:86-90
+        scale = num(t["scale"]) if "scale" in t else 10.0
+        odd = parse_vec3(t["odd"]) if "odd" in t else vmul(color, 0.2)
+        even = parse_vec3(t["even"]) if "even" in t else color
+        return ("checker", scale, odd, even)
+    scale = num(t["scale"]) if "scale" in t else 1.0
+    return (kind, scale, world.new_texture_perm())
+
+
+def _material(m, world=None):  # scene-loader.js:143-173 + materials.js constructors
     if not m or not isinstance(m, dict) or not truthy(m.get("type")):
         return ("lambertian", (0.8, 0.8, 0.8))
     t = _js_lower(m["type"], "material")
     if t == "lambertian":
-        return ("lambertian", parse_vec3(m.get("color")))
+        color = parse_vec3(m.get("color"))
+        tex = _texture(m, color, world)
+        return ("lambertian", color) if tex is None else ("lambertian", (0.0, 0.0, 0.0), tex)   # TexturedLambertian
     if t == "metal":
         r = m["roughness"] if "roughness" in m else 0.0
-        return ("metal", parse_vec3(m.get("color")), min(num(r), 1.0))  # Math.min(roughness, 1)
+        color = parse_vec3(m.get("color"))
+        tex = _texture(m, color, world)
+        if tex is not None:                                                   # TexturedMetal(texture, roughness)
+            return ("metal", (0.0, 0.0, 0.0), min(num(r), 1.0), tex)
+        return ("metal", color, min(num(r), 1.0))  # Math.min(roughness, 1)
     if t == "dielectric":
         return ("dielectric", num(m["ior"]) if "ior" in m else 1.5)
     if t == "emissive":
@@ -128,12 +157,22 @@ def _material(m):  # scene-loader.js:143-173 + materials.js constructors
 class World:
     """World (js/world.js:8-16): objects in insertion order, background, skyIntensity, perm."""
 
-    def __init__(self, perm):
+    def __init__(self, perm, texture_perm=None):
         self.objects = []      # (kind, material, payload)
         self.background = capi.RT_BG_GRADIENT
         self.sky_intensity = 1.0
         self.solid_color = (0.1, 0.1, 0.1)
         self.perm = list(perm)
+        # each NoiseTexture / MarbleTexture / WoodTexture owns a PerlinNoise (textures.js:43,57,72): the k-th
+        # one's table is texture_perm(k) (rng.texture_permutation under the render seed)
+        self.texture_perm = texture_perm
+        self.texture_perms = []
+
+    def new_texture_perm(self):
+        if self.texture_perm is None:
+            raise ValueError("noise-bearing textures need World(texture_perm=...)")
+        self.texture_perms.append(list(self.texture_perm(len(self.texture_perms))))
+        return len(self.texture_perms) - 1
 
     def add(self, kind, material, payload):
         self.objects.append((kind, material, payload))
@@ -176,8 +215,14 @@ def _create_object(o, world):  # scene-loader.js:90-137
         raise TypeError("Cannot read property 'type' of null")
     if not isinstance(o, dict) or not truthy(o.get("type")):
         return
-    mat = _material(o.get("material") if truthy(o.get("material")) else {"type": "lambertian", "color": [0.8, 0.8, 0.8]})
+    nperms = len(world.texture_perms)
+    mat = _material(o.get("material") if truthy(o.get("material")) else {"type": "lambertian", "color": [0.8, 0.8, 0.8]},
+                    world)
     t = _js_lower(o["type"], "object")
+    if t not in ("sphere", "plane", "box", "triangle", "mesh") or \
+            (t == "mesh" and (not truthy(o.get("vertices")) or not truthy(o.get("indices")))):
+        del world.texture_perms[nperms:]     # no object: its texture does not count (k follows World.objects)
+        return
     if t == "sphere":
         world.add("sphere", mat, (parse_vec3(o.get("center")), num(js_or(o.get("radius"), 1.0))))
     elif t == "plane":
@@ -209,14 +254,15 @@ def create_camera(cam, aspect):  # scene-loader.js:205-262
     return Camera(position, look_at, up, fov, final_aspect, aperture, focus, ctype)
 
 
-def load_from_json(data, width, height, perm):
-    """SceneLoader.loadFromJSON (scene-loader.js:20-84) -> (world, camera|None, new_dims|None)."""
+def load_from_json(data, width, height, perm, texture_perm=None):
+    """SceneLoader.loadFromJSON (scene-loader.js:20-84) -> (world, camera|None, new_dims|None).
+    texture_perm(k): the permutation of the k-th noise-bearing texture (scenes with "texture" entries)."""
     new_dims = None
     cam = data.get("camera")
     if truthy(cam) and truthy(cam.get("resolution")):
         new_dims = (int(cam["resolution"][0]), int(cam["resolution"][1]))
         width, height = new_dims
-    world = World(perm)
+    world = World(perm, texture_perm)
     bg = data.get("background")
     if truthy(bg):
         t = bg.get("type")
@@ -265,6 +311,16 @@ def setup_camera(cam, width, height):
 
 
 # ---- packing into rt_scene_desc ------------------------------------------------------------------
+_TEX_CODE = {"checker": capi.RT_TEX_CHECKER, "noise": capi.RT_TEX_NOISE, "marble": capi.RT_TEX_MARBLE,
+             "wood": capi.RT_TEX_WOOD}
+
+
+def material_texture(m):
+    """The texture tuple of a ("lambertian", albedo, texture) / ("metal", albedo, roughness, texture) material."""
+    n = {"lambertian": 2, "metal": 3}.get(m[0])
+    return m[n] if n is not None and len(m) > n else None
+
+
 _MAT_CODE = {"lambertian": capi.RT_MAT_LAMBERTIAN, "metal": capi.RT_MAT_METAL,
              "dielectric": capi.RT_MAT_DIELECTRIC, "emissive": capi.RT_MAT_EMISSIVE}
 
@@ -279,9 +335,17 @@ class PackedScene:
         mats, mat_index = [], {}
         objs = []
         tris = []
-        for kind, mat, payload in world.objects:
-            key = repr(mat)
+        # a textured scene keeps one material per object, like the JS packer (materials by identity) and the
+        # C++ loader, so the three hosts' material_texture arrays agree; plain scenes share equal materials
+        textured = any(material_texture(m) is not None for _, m, _ in world.objects)
+        textures, mat_tex = [], []
+        for oi, (kind, mat, payload) in enumerate(world.objects):
+            key = (oi, repr(mat)) if textured else repr(mat)
             if key not in mat_index:
+                tex = material_texture(mat)
+                mat_tex.append(-1 if tex is None else len(textures))
+                if tex is not None:
+                    textures.append(tex)
                 mat_index[key] = len(mats)
                 mats.append(mat)
             o = capi.ObjectDesc()
@@ -336,6 +400,26 @@ class PackedScene:
         d.sky_intensity = world.sky_intensity
         d.solid_color[:] = world.solid_color
         d.perm[:] = world.perm
+        # procedural textures (the fields appended behind perm)
+        tperms = getattr(world, "texture_perms", [])
+        self.textures = (capi.TextureDesc * max(1, len(textures)))()
+        for i, t in enumerate(textures):
+            td = self.textures[i]
+            td.type, td.scale = _TEX_CODE[t[0]], t[1]
+            if t[0] == "checker":
+                td.perm = -1
+                td.odd[:], td.even[:] = t[2], t[3]
+            else:
+                td.perm = t[2]
+        self.material_texture = np.array(mat_tex if mat_tex else [-1], dtype=np.int32)
+        self.texture_perms = np.array(tperms if tperms else [[0] * 512], dtype=np.int32).reshape(-1, 512)
+        self.num_textures, self.num_texture_perms = len(textures), len(tperms)
+        d.extensions = capi.RT_DESC_TEXTURES            # the five fields below are filled (zero counts: none)
+        d.num_textures = self.num_textures
+        d.num_texture_perms = self.num_texture_perms
+        d.textures = self.textures
+        d.material_texture = self.material_texture.ctypes.data_as(C.POINTER(C.c_int32))
+        d.texture_perms = self.texture_perms.ctypes.data_as(C.POINTER(C.c_int32))
 
     def record_bytes_per_segment(self):
         """Σ canonical record bytes over every primitive one world.hit call tests."""
@@ -368,3 +452,8 @@ def load_scene_json(name):
 
 def keyed_permutation(seed):
     return permutation(seed)
+
+
+def keyed_texture_permutation(seed):
+    """texture_perm argument of load_from_json / World for a render seed: k -> rng.texture_permutation(seed, k)"""
+    return lambda k: texture_permutation(seed, k)

@@ -27,8 +27,16 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 3      /* 2: rt_settings.device_count / devices (multi-GPU sample split)
+#define RT_ABI_VERSION 3      /* what rt_abi_version() returns: the generation of the calls and of every
+                                 struct field up to it (a caller built against it keeps working).
+                                 2: rt_settings.device_count / devices (multi-GPU sample split)
                                  3: rt_settings.sum_order, rt_output.preview_rgba8, rt_closest_hits */
+/* Procedural textures are an append-only extension of generation 3, not a new generation: nothing a
+ * generation-3 caller uses moved, and rt_scene_desc.abi_version stays RT_ABI_VERSION.  A caller that fills
+ * the texture fields appended behind `perm` says so in rt_scene_desc.extensions (formerly padding) with
+ * RT_DESC_TEXTURES; with any other value there the library reads nothing behind `perm`, so a binary built
+ * against the shorter struct stays valid.  rt_texture_desc and rt_texture_values come with it. */
+#define RT_DESC_TEXTURES 0x54455834   /* "TEX4" */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -54,6 +62,16 @@ typedef enum rt_material_type {
     RT_MAT_DIELECTRIC = 2, /* materials.js:45-84 */
     RT_MAT_EMISSIVE = 3    /* materials.js:87-96 */
 } rt_material_type;
+
+/* Procedural textures of TexturedLambertian / TexturedMetal (materials.js:99-126, textures.js:24-81).
+ * Every one depends on the hit point only (u, v are never set).  SolidColor and the base Texture are
+ * not listed: the host lowers them to the plain material's albedo. */
+typedef enum rt_texture_type {
+    RT_TEX_CHECKER = 0,   /* textures.js:24-36 */
+    RT_TEX_NOISE = 1,     /* textures.js:39-50 */
+    RT_TEX_MARBLE = 2,    /* textures.js:53-65 */
+    RT_TEX_WOOD = 3       /* textures.js:68-81 */
+} rt_texture_type;
 
 typedef enum rt_background_type {
     RT_BG_GRADIENT = 0,        /* World.skyGradient      world.js:35-40  */
@@ -109,6 +127,15 @@ typedef struct rt_object_desc {
     double g[6];           /* geometry, see rt_object_type */
 } rt_object_desc;          /* 64 bytes */
 
+typedef struct rt_texture_desc {
+    int32_t type;          /* rt_texture_type */
+    int32_t perm;          /* NOISE / MARBLE / WOOD: index of the texture's own PerlinNoise.p in
+                              rt_scene_desc.texture_perms; CHECKER: -1 */
+    double scale;          /* finite */
+    double odd[3];         /* CHECKER: colour where the product of sines is < 0 */
+    double even[3];        /* CHECKER: colour elsewhere (a NaN product included) */
+} rt_texture_desc;         /* 64 bytes */
+
 typedef struct rt_camera_desc {  /* vectors exactly as js/camera.js:8-36 computes them */
     double origin[3];
     double lower_left[3];
@@ -131,10 +158,22 @@ typedef struct rt_scene_desc {
                                             normalize(cross(v1-v0, v2-v0)) (geometry.js:143-145) */
     rt_camera_desc camera;
     int32_t background;                  /* rt_background_type */
-    int32_t _pad;
+    int32_t extensions;                  /* RT_DESC_TEXTURES: the fields behind `perm` are filled; anything else
+                                            (it was padding): they are not read */
     double sky_intensity;                /* World.skyIntensity */
     double solid_color[3];               /* RT_BG_SOLID color (updateBackground uses 0.1,0.1,0.1) */
     int32_t perm[512];                   /* World.cloudNoise.p (noise.js:6-18) */
+    /* extensions == RT_DESC_TEXTURES only (appended; every field above keeps its offset; not read
+     * otherwise).  A textured material keeps its type
+     * (RT_MAT_LAMBERTIAN / RT_MAT_METAL) and roughness; its attenuation is the texture's value at the hit
+     * point instead of albedo. */
+    int32_t num_textures;
+    int32_t num_texture_perms;
+    const rt_texture_desc* textures;     /* num_textures records */
+    const int32_t* material_texture;     /* num_materials entries: texture index, -1 = untextured; may be
+                                            NULL when num_textures == 0 */
+    const int32_t* texture_perms;        /* num_texture_perms x 512: each noise-bearing texture's own
+                                            PerlinNoise.p, entries in 0..255 */
 } rt_scene_desc;
 
 typedef struct rt_settings {
@@ -310,10 +349,17 @@ int rt_finalize_device(rt_scene* scene, const rt_settings* settings, const doubl
 int rt_closest_hits(rt_scene* scene, int32_t precision, int32_t accel, const double* rays, size_t n,
                     double* t, int32_t* kind, int32_t* index);
 
+/* Diagnostic (tests): Texture.value(u, v, p) of texture `texture` at `n` host points (n x 3 doubles; rounded
+ * to binary32 first in RT_PREC_F32) evaluated on the scene's device by the function the trace kernels call;
+ * rgb: host, n x 3 doubles.  RT_ERR_INVALID unless 0 <= texture < num_textures. */
+int rt_texture_values(rt_scene* scene, int32_t precision, int32_t texture, const double* points, size_t n,
+                      double* rgb);
+
 /* Diagnostic: the walk a render with these precision / accel settings runs on this scene — 0 World.objects
  * order (brute force), 1 a BVH tree walk, 2 the uniform grid over the spheres (sphere-only scenes where
- * the host's sampled cost estimate prefers it, scene_pack.h choose_walk); < 0 an error status.  Every
- * walk finds the same closest hit; they differ in speed only. */
+ * the host's sampled cost estimate prefers it, scene_pack.h choose_walk; never for a scene with textures,
+ * whose kernels walk World order or the trees); < 0 an error status.  Every walk finds the same closest
+ * hit; they differ in speed only. */
 int rt_scene_walk(rt_scene* scene, int32_t precision, int32_t accel);
 
 /* Request cancellation of an in-flight rt_render on `scene` (the pool kernels read it between items;
