@@ -1647,7 +1647,9 @@ __device__ __forceinline__ double post_channel(const FinalizeParams& p, double c
     if (p.tone_map == 1) tm = js_max<double>(0.0, (x * (2.51 * x + 0.03)) / (x * (2.43 * x + 0.59) + 0.14));
     else if (p.tone_map == 2) tm = x;
     else tm = x / (1.0 + x);
-    return jsm::pow(js_max<double>(0.0, tm), inv_gamma);      // post-processor.js:38, V8's Math.pow (js_math.h)
+    // post-processor.js:38, V8's Math.pow (js_math.h).  Math.max(0, -0) is +0 where js_max gives -0, and an
+    // odd integer 1/gamma (gamma 1) keeps that sign in the Float32 frame: + 0.0 makes it +0
+    return jsm::pow(js_max<double>(0.0, tm) + 0.0, inv_gamma);
 }
 
 __global__ __launch_bounds__(64) void finalize_kernel(const FinalizeParams p, const double* __restrict__ sum,

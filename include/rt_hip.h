@@ -232,8 +232,9 @@ typedef struct rt_output {
                                  more than one sample batch, before every progress() call this buffer holds
                                  the RGBA8 frame of the samples traced so far (mean over those samples, tone
                                  map, gamma; no denoise, like the reference's rows before its final pass;
-                                 the gamma pow of these running frames is binary32, so a pixel within ~1e-7 of
-                                 an RGBA8 rounding boundary may differ by one step from rgba8's exact frame).
+                                 these running frames take the bytes from per-gamma thresholds computed with
+                                 the binary64 pow of the exact epilogue, so they equal the rgba8 frame a
+                                 render of exactly those samples gives, byte for byte).
                                  After a cancel the buffer holds the exact frame of the checkpointed samples.  A batch
                                  whose successor has already finished when the host gets to it is skipped
                                  (the buffer keeps the previous frame until the newer one is copied) */

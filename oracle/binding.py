@@ -33,6 +33,8 @@ def lib():
         L.orc_render.argtypes = [C.POINTER(capi.SceneDesc), C.POINTER(capi.Settings), dp, dp,
                                  C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.orc_render.restype = C.c_int
+        L.orc_finalize.argtypes = [C.POINTER(capi.Settings), dp, C.c_size_t, dp, dp, C.POINTER(C.c_uint8)]
+        L.orc_finalize.restype = None
         L.orc_kat_hit.argtypes = [C.c_int, dp, C.c_int, dp, dp, C.c_double, C.c_double, C.POINTER(HitOut)]
         L.orc_kat_scatter.argtypes = [C.POINTER(capi.MaterialDesc), dp, dp, dp, C.c_int, C.c_uint32, C.c_uint32,
                                       C.c_uint32, dp, dp, dp, C.POINTER(C.c_uint32)]
@@ -70,6 +72,17 @@ def denoise(post, settings):
     rgba = np.full((h, w, 4), 255, dtype=np.uint8)
     rgba[..., :3] = np.where(np.isnan(v), 0, np.clip(v, 0, 255)).astype(np.uint8)
     return out, rgba
+
+
+def finalize(sums, settings):
+    """The oracle's epilogue (orc_finalize: mean, tone map, gamma, RGBA8) of n pixels' sample sums, an
+    array of 3n binary64 -> (mean (n, 3), post (n, 3) binary64, rgba8 (n, 4))."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1, 3)
+    n = sums.shape[0]
+    mean, post = np.zeros((n, 3)), np.zeros((n, 3))
+    rgba = np.zeros((n, 4), dtype=np.uint8)
+    lib().orc_finalize(C.byref(settings), _p(sums), n, _p(mean), _p(post), _p(rgba, C.c_uint8))
+    return mean, post, rgba
 
 
 def render(packed, settings):

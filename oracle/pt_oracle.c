@@ -607,6 +607,27 @@ static uint8_t to_u8(double c) {                                                
     return v != v ? 0 : (uint8_t)v;                                                       /* Uint8ClampedArray(NaN) = 0 */
 }
 
+/* The epilogue of n pixels from their sample sums (3 per pixel): mean = sum / sampleCount, toneMap,
+ * gammaCorrect, RGBA8 (ray-tracer.js:208-252).  mean and post (3 doubles per pixel) and rgba (4 bytes per
+ * pixel) are optional (NULL). */
+void orc_finalize(const rt_settings* st, const double* sum, size_t n, double* mean, double* post, uint8_t* rgba) {
+    int S = st->samples;   /* sampleCount, resolved by the host (ray-tracer.js:201) */
+    for (size_t q = 0; q < n; q++) {
+        V3 color = vdiv(vld(sum + 3 * q), S);
+        double c[3] = {color.x, color.y, color.z}, tm[3], g[3];
+        if (mean) memcpy(mean + 3 * q, c, sizeof c);
+        orc_tone_map(st->tone_map, st->exposure, c, tm);
+        orc_gamma(st->gamma, tm, g);
+        if (post) memcpy(post + 3 * q, g, sizeof g);
+        if (rgba) {
+            rgba[4 * q] = to_u8(g[0]);
+            rgba[4 * q + 1] = to_u8(g[1]);
+            rgba[4 * q + 2] = to_u8(g[2]);
+            rgba[4 * q + 3] = 255;
+        }
+    }
+}
+
 /* Render the crop window of settings; outputs optional (NULL). */
 int orc_render(const rt_scene_desc* sc, const rt_settings* st, double* mean, double* post, uint8_t* rgba,
                uint32_t* segs, uint32_t* draws) {
@@ -633,18 +654,8 @@ int orc_render(const rt_scene_desc* sc, const rt_settings* st, double* mean, dou
                 orc_camera_ray(&sc->camera, u, v, &rng, o, d);
                 color = vadd(color, ray_color(sc, vld(o), vld(d), st->max_depth, &rng, sp));
             }
-            color = vdiv(color, S);
-            double c[3] = {color.x, color.y, color.z}, tm[3], g[3];
-            if (mean) memcpy(mean + 3 * q, c, sizeof c);
-            orc_tone_map(st->tone_map, st->exposure, c, tm);
-            orc_gamma(st->gamma, tm, g);
-            if (post) memcpy(post + 3 * q, g, sizeof g);
-            if (rgba) {
-                rgba[4 * q] = to_u8(g[0]);
-                rgba[4 * q + 1] = to_u8(g[1]);
-                rgba[4 * q + 2] = to_u8(g[2]);
-                rgba[4 * q + 3] = 255;
-            }
+            double c[3] = {color.x, color.y, color.z};
+            orc_finalize(st, c, 1, mean ? mean + 3 * q : NULL, post ? post + 3 * q : NULL, rgba ? rgba + 4 * q : NULL);
         }
     }
     return 0;
