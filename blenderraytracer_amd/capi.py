@@ -11,6 +11,8 @@ LIB_PATH = os.path.join(HERE, "lib", "librt_hip.so")
 
 RT_ABI_VERSION = 3            # rt_abi_version()
 RT_DESC_TEXTURES = 0x54455834  # rt_scene_desc.extensions of a descriptor whose texture fields are filled
+RT_DESC_LIGHTS = 0x4C495434    # ... whose texture fields and light fields are filled
+RT_MAX_LIGHTS = 32
 RT_MAX_DEVICES = 8
 
 # enums (include/rt_hip.h)
@@ -24,6 +26,7 @@ RT_PREC_F64, RT_PREC_F32 = range(2)
 RT_ACCEL_AUTO, RT_ACCEL_BRUTE, RT_ACCEL_BVH = range(3)
 RT_SUM_POOL, RT_SUM_SAMPLE_ORDER = range(2)
 RT_TEX_CHECKER, RT_TEX_NOISE, RT_TEX_MARBLE, RT_TEX_WOOD = range(4)
+RT_LIGHT_POINT, RT_LIGHT_DIRECTIONAL = range(2)
 
 STATUS = {0: "RT_OK", -1: "RT_ERR_INVALID", -2: "RT_ERR_DEVICE", -3: "RT_ERR_NOMEM",
           -4: "RT_ERR_CANCELLED", -5: "RT_ERR_NO_DEVICE"}
@@ -44,6 +47,11 @@ class TextureDesc(C.Structure):
                 ("even", C.c_double * 3)]
 
 
+class LightDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("_pad", C.c_int32), ("v", C.c_double * 3), ("color", C.c_double * 3),
+                ("intensity", C.c_double)]
+
+
 class CameraDesc(C.Structure):
     _fields_ = [("origin", C.c_double * 3), ("lower_left", C.c_double * 3), ("horizontal", C.c_double * 3),
                 ("vertical", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3),
@@ -58,7 +66,8 @@ class SceneDesc(C.Structure):
                 ("sky_intensity", C.c_double), ("solid_color", C.c_double * 3), ("perm", C.c_int32 * 512),
                 ("num_textures", C.c_int32), ("num_texture_perms", C.c_int32),
                 ("textures", C.POINTER(TextureDesc)), ("material_texture", C.POINTER(C.c_int32)),
-                ("texture_perms", C.POINTER(C.c_int32))]
+                ("texture_perms", C.POINTER(C.c_int32)),
+                ("num_lights", C.c_int32), ("_pad2", C.c_int32), ("lights", C.POINTER(LightDesc))]
 
 
 class Settings(C.Structure):
@@ -105,6 +114,8 @@ EXPORTS = {
     "rt_cancel": (C.c_int, [C.c_void_p]),
     "rt_closest_hits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_size_t,
                                   C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rt_occluded": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_size_t,
+                              C.POINTER(C.c_uint8)]),
     "rt_texture_values": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_size_t,
                                     C.POINTER(C.c_double)]),
     "rt_scene_walk": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -114,6 +125,7 @@ EXPORTS = {
     # include/rt_scene_json.h (host-only scene-JSON loader)
     "rt_json_scene_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_json_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),
+    "rt_json_scene_desc_lit": (C.POINTER(SceneDesc), [C.c_void_p]),
     "rt_json_scene_size": (None, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rt_json_scene_destroy": (None, [C.c_void_p]),
 }

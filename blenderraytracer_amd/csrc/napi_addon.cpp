@@ -205,6 +205,13 @@ napi_value create_scene(napi_env env, napi_callback_info info) {
         desc.texture_perms = static_cast<const int32_t*>(p);
         desc.num_texture_perms = (int32_t)(n / (512 * sizeof(int32_t)));
     }
+    // scene lights (pack.mjs with { lights: true }): rt_light_desc records; direct lighting when there is one
+    if (get_bytes(env, d, "lights", &p, &n) && n >= sizeof(rt_light_desc)) {
+        if (n % sizeof(rt_light_desc)) return throw_err(env, "desc.lights must hold 64-byte rt_light_desc records");
+        desc.lights = static_cast<const rt_light_desc*>(p);
+        desc.num_lights = (int32_t)(n / sizeof(rt_light_desc));
+        desc.extensions = RT_DESC_LIGHTS;
+    }
     rt_scene* sc = nullptr;
     if (rt_scene_create(&desc, device, &sc) != RT_OK) return throw_err(env, std::string("rt_scene_create: ") + rt_last_error());
     SceneBox* box = new SceneBox();

@@ -246,6 +246,12 @@ enum TexType : int { TEX_CHECKER = 0, TEX_NOISE = 1, TEX_MARBLE = 2, TEX_WOOD = 
 template <class R> struct TexRec { int type, perm; R scale; R odd[3], even[3]; };
 // Everything a textured scene adds, behind SceneView::tex: mat_tex[m] = the texture of material m, -1 none
 template <class R> struct TexView { const TexRec<R>* recs; const int* perms; const int* mat_tex; int num, num_perms; };
+// Scene lights (lights.js): v = PointLight.position, or DirectionalLight.direction as its constructor normalized
+// it.  The LightView of a lit scene sits behind its TexView (light_view); a lit scene always has a TexView
+// (mat_tex all -1 without textures), since its kernels are compiled for textures too.
+enum LightType : int { LIGHT_POINT = 0, LIGHT_DIRECTIONAL = 1 };
+template <class R> struct LightRec { int type, pad; R v[3]; R color[3]; R intensity; };
+template <class R> struct LightView { const LightRec<R>* recs; int num, pad; };
 
 template <class R>
 struct SceneView {
@@ -280,6 +286,8 @@ struct SceneView {
     const SphereLeaf<R>* bvh_sphere_leaf;
     const BvhNode* tri_nodes;
     int num_tri_nodes;
+    int num_lights;                // scene lights of a render with direct lighting (0: none; only then do the
+                                   // F_LIGHT kernels run).  Like num_tex it fills 4 padding bytes
     const TriLeaf<R>* bvh_tri_leaf;
     const TriFilter* tri_filter;   // binary64: the triangle leaves' binary32 pre-filter records (same order)
     const Bvh2Node* sphere_wide;   // two-child nodes of the two trees (preorder)
@@ -320,6 +328,14 @@ static_assert(offsetof(SceneView<double>, perm) == offsetof(SceneView<double>, n
 constexpr int kTexViewAt = 512;
 template <class R> RT_HD const TexView<R>* tex_view(const SceneView<R>& sc) {
     return reinterpret_cast<const TexView<R>*>(sc.perm + kTexViewAt);
+}
+// num_lights sits in padding too, and the LightView of a lit scene follows its TexView behind `perm`
+static_assert(offsetof(SceneView<double>, bvh_tri_leaf) == offsetof(SceneView<double>, num_tri_nodes) + 8 &&
+              offsetof(SceneView<float>, bvh_tri_leaf) == offsetof(SceneView<float>, num_tri_nodes) + 8, "num_lights fills padding");
+static_assert(sizeof(TexView<double>) == 32 && sizeof(TexView<float>) == 32, "TexView in 8 ints");
+constexpr int kLightViewAt = kTexViewAt + 8;
+template <class R> RT_HD const LightView<R>* light_view(const SceneView<R>& sc) {
+    return reinterpret_cast<const LightView<R>*>(sc.perm + kLightViewAt);
 }
 
 enum HitKind : int { HIT_NONE = -1, HIT_SPHERE = 0, HIT_PLANE = 1, HIT_BOX = 2, HIT_TRI = 3 };
@@ -482,7 +498,8 @@ RT_HD bool sphere_filter_pass(const SphereFilter& s, const FilterRay& r) {
 // supersampling).  A kernel compiled without a feature holds none of its code, nor the scene constants
 // that code reads, so fewer scalars stay live across the segment loop (SGPR spills).
 enum Feat : int { F_PLANES = 1, F_BOXES = 2, F_TRIS = 4, F_BGALL = 8, F_CAMALL = 16, F_ALL = 31,
-                  F_TEX = 32 };   // F_TEX: textured Lambertian / Metal (not part of F_ALL: a kernel of its own)
+                  F_TEX = 32,     // F_TEX: textured Lambertian / Metal (not part of F_ALL: a kernel of its own)
+                  F_LIGHT = 64 }; // F_LIGHT: direct lighting from the scene's lights (kernels of their own, with F_TEX)
 
 // Closest hit over the whole world: World.hit (world.js:20-33) with every object's hit() inlined.
 // All lanes walk the same primitive list in the same order, so every record load — including the
@@ -1315,10 +1332,14 @@ RT_HD Closest<R> closest_hit_grid(const SceneView<R>& sc, V3<R> o, V3<R> d, Work
 // textures (F_ALL | F_TEX); every other mode is compiled without texture code
 enum Accel : int { ACC_BRUTE = 0, ACC_BRUTE_LEAN = 1, ACC_BVH = 2, ACC_BVH_STACK = 3, ACC_BVH_SPHERES = 4, ACC_BVH_SPHERES_LDS = 5,
                    ACC_GRID = 6, ACC_GRID_LDS = 7, ACC_BVH_TRI_LDS = 8, ACC_GRID_LDS_LEAN = 9,
-                   ACC_BVH_STACK_LEAN = 10, ACC_BRUTE_TEX = 11, ACC_BVH_STACK_TEX = 12 };
-// the walk a mode runs (the textured modes walk like their untextured twins)
+                   ACC_BVH_STACK_LEAN = 10, ACC_BRUTE_TEX = 11, ACC_BVH_STACK_TEX = 12,
+                   ACC_BRUTE_LIT = 13, ACC_BVH_STACK_LIT = 14 };
+// ACC_BRUTE_LIT / ACC_BVH_STACK_LIT: the same two walks for renders with direct lighting (F_ALL | F_TEX |
+// F_LIGHT: a textured lit scene needs no third variant)
+// the walk a mode runs (the textured and lit modes walk like their plain twins)
 template <int ACC> constexpr int walk_of() {
-    return ACC == ACC_BRUTE_TEX ? ACC_BRUTE : ACC == ACC_BVH_STACK_TEX ? ACC_BVH_STACK : ACC;
+    return ACC == ACC_BRUTE_TEX || ACC == ACC_BRUTE_LIT ? ACC_BRUTE
+         : ACC == ACC_BVH_STACK_TEX || ACC == ACC_BVH_STACK_LIT ? ACC_BVH_STACK : ACC;
 }
 // The lean kernels (pt_trace.hip scene_feat): compiled for the common scene shapes only, the sky
 // gradient, the perspective camera and supersampling AA —
@@ -1327,7 +1348,8 @@ template <int ACC> constexpr int walk_of() {
 //   ACC_BRUTE_LEAN: World order for spheres and planes (config 2's Cornell box)
 template <int ACC> constexpr int feat_of() {
     return ACC == ACC_GRID_LDS_LEAN ? 0 : ACC == ACC_BVH_STACK_LEAN ? (F_PLANES | F_TRIS)
-         : ACC == ACC_BRUTE_LEAN ? F_PLANES : ACC == ACC_BRUTE_TEX || ACC == ACC_BVH_STACK_TEX ? (F_ALL | F_TEX) : F_ALL;
+         : ACC == ACC_BRUTE_LEAN ? F_PLANES : ACC == ACC_BRUTE_TEX || ACC == ACC_BVH_STACK_TEX ? (F_ALL | F_TEX)
+         : ACC == ACC_BRUTE_LIT || ACC == ACC_BVH_STACK_LIT ? (F_ALL | F_TEX | F_LIGHT) : F_ALL;
 }
 
 // RT_SC_RELOAD (bit mask of lean kernels: 1 tree, 2 grid, 4 brute force; default 2): the closest-hit
@@ -1371,6 +1393,151 @@ RT_HD Closest<R> closest_hit_acc(const SceneView<R>& sc, V3<R> o, V3<R> d, Work&
         return closest_hit_bvh<R, true, true, false, false, feat_of<ACC>()>(sc, o, d, w, stk, skip_tri);
     else if constexpr (ACC == ACC_BVH_TRI_LDS) return closest_hit_bvh<R, true, true, false, true>(sc, o, d, w, stk);
     else return closest_hit_runs<R, feat_of<ACC>()>(sc, o, d);
+}
+
+// ---- occlusion (any-hit) query: the shadow rays of direct lighting ----------------------------------------
+// World.hit(ray, 0.001, tmax) !== null (world.js:20-33): World.hit starts from closestT = tMax and accepts
+// strictly smaller t, and every object's candidate t is independent of tMax (closest_hit_bvh's comment), so
+// the verdict is "some candidate t < tmax" = "the closest hit exists and has t < tmax".  Both forms below run
+// the closest-hit query's own per-primitive tests against a best that starts at (tmax, no hit) — in the tree
+// form with obj = -1, so that `better` accepts no tie at tmax — and stop at the first accepted primitive.
+// A candidate at t == tmax does not occlude; a Box's NaN t is never accepted; tmax = +inf (a directional
+// light) is World.hit's own start.  The binary32 pre-filters and the nodes' slab tests only reject (their
+// bounds hold for any ray limit: the limit enters as bvh_tlimit(tmax) >= tmax).  tri_exit_bound is not used:
+// a shadow ray starts at a hit point of any primitive in any direction.
+template <class R, int FEAT = F_ALL>
+RT_HD bool occluded_runs(const SceneView<R>& sc, V3<R> o, V3<R> d, R tmax) {
+    const R tmin = (R)0.001;
+    Closest<R> b{tmax, HIT_NONE, 0, 0};
+    const R a = dot(d, d);
+    for (int r = 0; r < sc.num_runs; ++r) {
+        const Run run = sc.runs[r];
+        if (run.kind == RUN_SPHERES) {
+            if constexpr (sizeof(R) == 8) {
+                const FilterRay fr = make_filter_ray(o, d);
+                for (int i = run.begin; i < run.end; ++i) {
+                    if (!sphere_filter_pass(sc.sphere_filter[i], fr)) continue;
+                    sphere_test_f64(sc, o, d, a, tmin, i, b);
+                    if (b.kind != HIT_NONE) return true;
+                }
+                continue;
+            }
+            for (int i = run.begin; i < run.end; ++i) {
+                sphere_test_f64(sc, o, d, a, tmin, i, b);
+                if (b.kind != HIT_NONE) return true;
+            }
+        } else if ((FEAT & F_PLANES) != 0 && run.kind == RUN_PLANES) {
+            for (int i = run.begin; i < run.end; ++i) {                       // geometry.js:56-74
+                const PlaneRec<R> p = sc.planes[i];
+                R denom = p.nx * d.x + p.ny * d.y + p.nz * d.z;
+                if (fabs(denom) < (R)1e-6) continue;
+                R t = ((p.px - o.x) * p.nx + (p.py - o.y) * p.ny + (p.pz - o.z) * p.nz) / denom;
+                if (t < tmin || t > tmax) continue;
+                if (t < tmax) return true;
+            }
+        } else if ((FEAT & F_BOXES) != 0 && run.kind == RUN_BOXES) {
+            for (int i = run.begin; i < run.end; ++i) {                       // geometry.js:85-117
+                const BoxRec<R> bx = sc.boxes[i];
+                R t0 = (bx.mnx - o.x) / d.x, t1 = (bx.mxx - o.x) / d.x;
+                if (t0 > t1) { R s = t0; t0 = t1; t1 = s; }
+                R ty0 = (bx.mny - o.y) / d.y, ty1 = (bx.mxy - o.y) / d.y;
+                if (ty0 > ty1) { R s = ty0; ty0 = ty1; ty1 = s; }
+                if (t0 > ty1 || ty0 > t1) continue;
+                t0 = js_max(t0, ty0);
+                t1 = js_min(t1, ty1);
+                R tz0 = (bx.mnz - o.z) / d.z, tz1 = (bx.mxz - o.z) / d.z;
+                if (tz0 > tz1) { R s = tz0; tz0 = tz1; tz1 = s; }
+                if (t0 > tz1 || tz0 > t1) continue;
+                t0 = js_max(t0, tz0);
+                t1 = js_min(t1, tz1);
+                R t = t0 > tmin ? t0 : t1;
+                if (t < tmin || t > tmax) continue;                           // NaN passes here ...
+                if (t < tmax) return true;                                    // ... and fails here
+            }
+        } else if ((FEAT & F_TRIS) != 0) {                                    // geometry.js:148-188, 248-262
+            const bool mesh = run.kind == RUN_MESH;
+            R local = tmax;                                                   // a mesh accepts <=, World.hit then <
+            for (int i = run.begin; i < run.end; ++i) {
+                R t;
+                if (!triangle_candidate(sc.tris[i], o, d, tmin, t)) continue;
+                if (t > local) continue;
+                if (mesh) local = t;
+                if (t < tmax) return true;
+            }
+        }
+    }
+    return false;
+}
+
+// Single exit: a lane that has its verdict stays in the function with its limit collapsed below every node's
+// entry (tl = -1), so it enters no node, a leaf still on its stack changes nothing that matters (b only ever
+// holds an accepted primitive), and it leaves each walk at once.  What bvh_walk needs from a caller is only
+// what closest_hit_bvh gives it too: tl never grows during a walk, and leaf() may lower it.  Its ballot /
+// readfirstlane reads act over the active lanes, so calling it under divergent control flow (direct_light's
+// loop does) is within its contract.  A variant with `return true` between the phases was tried once and
+// miscompared on the device; the cause was not established ("Direct lighting"), and this form
+// does not rest on any guess about it: it is the closest-hit walk with a collapsing limit.
+template <class R, bool WIDE, int FEAT = F_ALL>
+RT_HD bool occluded_bvh(const SceneView<R>& sc, V3<R> o, V3<R> d, R tmax, Work& w, BvhStack stk) {
+    const R tmin = (R)0.001;
+    Closest<R> b{tmax, HIT_NONE, 0, 0, -1};
+    brute_planes_boxes<R, FEAT>(sc, o, d, tmin, b);
+    const BvhRay br = make_bvh_ray(o, d);
+    float tl = bvh_tlimit(tmax);
+    if (b.kind != HIT_NONE) tl = -1.0f;
+    if (sc.num_sphere_nodes > 0 || sc.num_big_spheres > 0) {
+        const R a = dot(d, d);
+        FilterRay fr{};
+        if constexpr (sizeof(R) == 8) fr = make_filter_ray(o, d);
+        if (sc.num_big_spheres > 0) {
+            sphere_records(sc.big_spheres, 0, sc.num_big_spheres, o, d, a, fr, tmin, b, tl, w, true);
+            if (b.kind != HIT_NONE) tl = -1.0f;
+        }
+        auto leaf = [&](int fc) {
+            sphere_leaf(sc, fc, o, d, a, fr, tmin, b, tl, w);
+            if (b.kind != HIT_NONE) tl = -1.0f;
+        };
+        if (sc.num_sphere_nodes > 0)
+            bvh_walk<WIDE, 0>(sc.sphere_nodes, sc.num_sphere_nodes, sc.sphere_wide, br, tl, stk, w, leaf);
+    }
+    if (sc.num_tri_nodes > 0) {
+        auto leaf = [&](int fc) {
+            tri_leaf(sc, fc, o, d, tmin, b, tl, w);
+            if (b.kind != HIT_NONE) tl = -1.0f;
+        };
+        bvh_walk<WIDE, 0>(sc.tri_nodes, sc.num_tri_nodes, sc.tri_wide, br, tl, stk, w, leaf);
+    }
+    return b.kind != HIT_NONE;
+}
+
+// The occlusion query of mode ACC's walk (World order, or the two trees)
+template <class R, int ACC>
+RT_HD bool occluded(const SceneView<R>& sc, V3<R> o, V3<R> d, R tmax, Work& w, BvhStack stk) {
+    static_assert(walk_of<ACC>() == ACC_BRUTE || walk_of<ACC>() == ACC_BVH || walk_of<ACC>() == ACC_BVH_STACK,
+                  "occlusion queries walk World order or the trees");
+    if constexpr (walk_of<ACC>() == ACC_BRUTE) return occluded_runs<R, F_ALL>(sc, o, d, tmax);
+    else return occluded_bvh<R, walk_of<ACC>() == ACC_BVH_STACK, F_ALL>(sc, o, d, tmax, w, stk);
+}
+
+// PointLight.illuminate / DirectionalLight.illuminate (lights.js:22-46) in the reference's evaluation order
+template <class R> struct Illum { V3<R> dir, col; R dist; };
+template <class R>
+RT_HD Illum<R> illuminate(const LightRec<R>& l, V3<R> p) {
+    Illum<R> il;
+    const V3<R> c = mk(l.color[0], l.color[1], l.color[2]);
+    if (l.type == LIGHT_POINT) {
+        const V3<R> dv = mk(l.v[0], l.v[1], l.v[2]) - p;
+        const R dist = sqrt(dv.x * dv.x + dv.y * dv.y + dv.z * dv.z);
+        const R att = (R)1.0 / (((R)1.0 + (R)0.1 * dist) + ((R)0.01 * dist) * dist);
+        il.dir = dist > (R)0 ? vdiv(dv, dist) : mk<R>(0, 0, 0);                // Vec3.normalize (math.js:18)
+        il.col = c * (l.intensity * att);
+        il.dist = dist;
+    } else {
+        il.dir = mk(l.v[0], l.v[1], l.v[2]) * (R)-1;
+        il.col = c * l.intensity;
+        il.dist = (R)INFINITY;
+    }
+    return il;
 }
 
 template <class R>

@@ -123,6 +123,12 @@ template <class R>
 hipError_t launch_closest_hits(const SceneView<R>& sc, bool bvh, const double* rays, size_t n, double* t, int* kind,
                                int* idx, hipStream_t stream);
 
+// World.hit(ray, 0.001, tmax[i]) !== null of n rays (n x 6 doubles and n doubles, device) -> out (n bytes,
+// device): rt_occluded, the lit trace kernels' any-hit query (bvh: the trees, else World order)
+template <class R>
+hipError_t launch_occluded(const SceneView<R>& sc, bool bvh, const double* rays, const double* tmax, size_t n,
+                           uint8_t* out, hipStream_t stream);
+
 // Texture.value of texture `tex` at n points (n x 3 doubles, device) -> rgb (n x 3 doubles, device):
 // rt_texture_values.  The scene must have textures (sc.tex), tex in [0, num_textures)
 template <class R>

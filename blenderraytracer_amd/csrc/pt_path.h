@@ -8,6 +8,8 @@
 // recursion's att_0*(att_1*(...*E)): the same factors, rounded in a different order (<= a few ulp);
 // every path DECISION is unaffected.
 #pragma once
+#include <type_traits>
+
 #include "pt_core.h"
 
 namespace rt {
@@ -258,12 +260,41 @@ RT_HD bool scatter(const MatRec<R>& m, const Hit<R>& h, V3<R> unit, V3<R> p, Rng
 
 struct PixelResult { uint32_t segments, draws; Work work; uint64_t cyc[3]; };
 
+// Direct lighting at a Lambertian / TexturedLambertian hit (F_LIGHT): for every scene light in scene order,
+// light.illuminate(hit.point), the cosine against the stored (face-oriented) normal, a shadow ray from the
+// hit point towards the light (occluded: World.hit(ray, 0.001, distance) !== null), and
+// direct += (att * color) * cos per channel.  No random draw, no segment: path decisions are untouched.
+// `direct` starts at +0 and only adds, so no component is ever -0.
+template <class R, int ACC>
+RT_HD V3<R> direct_light(const SceneView<R>& sc, const Hit<R>& h, V3<R> att, Work& w, BvhStack stk) {
+    const LightView<R>* lv = light_view(sc);
+    V3<R> direct = mk<R>(0, 0, 0);
+    for (int i = 0; i < lv->num; ++i) {
+        const Illum<R> il = illuminate<R>(lv->recs[i], h.p);
+        const R cs = dot(h.n, il.dir);
+        if (!(cs > (R)0)) continue;                                           // NaN and a zero direction too
+        if (occluded<R, ACC>(sc, h.p, il.dir, il.dist, w, stk)) continue;
+        direct = direct + mk((att.x * il.col.x) * cs, (att.y * il.col.y) * cs, (att.z * il.col.z) * cs);
+    }
+    return direct;
+}
+
 // Shade the segment whose closest hit is c (rayColor's body after world.hit, ray-tracer.js:106-122):
 // emission / scatter / background.  Returns true when the sample's path ended; its radiance L is
 // then in `L`, otherwise (o, d, T, depth) describe the next segment.
-template <class R, int FEAT = F_ALL>
+// F_LIGHT (the lit kernels; ACC: their walk, for the shadow rays): a scattering Lambertian hit adds
+// T (.) direct to lc->dsum, with T the throughput before this hit's attenuation (the forward form of
+// emitted + direct + attenuation * rayColor(scattered)).
+// LightCtx: what the lit kernels hand to shade_segment — the running sum, the work counters the shadow rays
+// count in, and the lane's traversal stack (idle while a segment is shaded).  One pointer, nullptr elsewhere:
+// further by-value parameters changed the register allocation of kernels that never use them.
+template <class R> struct LightCtx { V3<R> dsum; Work* w; BvhStack stk; };
+// the kernels' LightCtx variable: an empty object in the instantiations without F_LIGHT
+struct NoLightCtx { template <class... A> RT_HD NoLightCtx(A&&...) {} };
+template <class R, bool LIT> using LightState = std::conditional_t<LIT, LightCtx<R>, NoLightCtx>;
+template <class R, int FEAT = F_ALL, int ACC = ACC_BRUTE>
 RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, V3<R>& d, V3<R>& T, int& depth,
-                         Rng<R>& g, V3<R>& L, const MatRec<R>* mats = nullptr) {
+                         Rng<R>& g, V3<R>& L, const MatRec<R>* mats = nullptr, LightCtx<R>* lc = nullptr) {
     bool done = true;
     L = mk<R>(0, 0, 0);
     const bool hit = c.kind != HIT_NONE;
@@ -295,6 +326,12 @@ RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, 
                         if (tex >= 0) att = texture_value<R>(tv, tex, h.p);
                     }
                 }
+                if constexpr ((FEAT & F_LIGHT) != 0) {
+                    if (m.type == 0) {
+                        const V3<R> dl = direct_light<R, ACC>(sc, h, att, *lc->w, lc->stk);
+                        lc->dsum = lc->dsum + mk(T.x * dl.x, T.y * dl.y, T.z * dl.z);
+                    }
+                }
                 T = mk(T.x * att.x, T.y * att.y, T.z * att.z);
                 o = h.p;
                 d = nd;
@@ -317,12 +354,88 @@ RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, 
 // zero for every material that scatters (an Emissive hit ends the path), so this is the recursion's
 // value bit for bit; with the samples added in sample order (this function) the means are the
 // reference's.  Deeper renders carry the throughput forward.
+// Lit modes (F_LIGHT) keep one direct term per scattering bounce beside att[] — the last allowed bounce's
+// too, whose recursive call returns 0 — and fold direct_k + att_k * (...) from the last bounce back: emitted
+// is +0 there and direct is never -0, so (e + direct) + att * rec is that sum bit for bit.
 #ifndef RT_REC_DEPTH
 #define RT_REC_DEPTH 16
 #endif
+// trace_pixel for the lit modes (F_LIGHT): the same loop with the direct terms.  A twin, not `if constexpr`
+// branches inside trace_pixel: the folded form (discarded branches, a one-element dir[], an empty LightState)
+// is the same program for the unlit modes, yet it changed the register allocation of 21 existing
+// lane-per-pixel trace_kernel instantiations — trace_kernel<float, *, ACC_BVH> from no scratch to 32-48 B
+// and 7-10 spilled VGPRs, trace_kernel<double, false, ACC_BRUTE> from 592 to 608 B (compiler resource
+// remarks, DESIGN.md §4 "Direct lighting") — and the feature must leave every existing kernel as it was.
+template <class R, bool COUNT, int ACC>
+RT_HD PixelResult trace_pixel_lit(const SceneView<R>& sc, const ImageParams& im, int cx, int cy, int s_end, double* sum,
+                                  BvhStack stk) {
+    const int i = im.x0 + cx, row = im.y0 + cy, j = im.height - 1 - row;
+    const uint32_t pkey = pixel_key(im.seedm, (uint32_t)row * (uint32_t)im.width + (uint32_t)i);
+    PixelResult res{0, 0, {0, 0, 0}, {0, 0, 0}};
+    int s = im.s_begin;
+    double sx = sum[0], sy = sum[1], sz = sum[2];
+    Rng<R> g;
+    V3<R> o, d, T = mk<R>(1, 1, 1);
+    int depth = im.max_depth;
+    const bool rec = sizeof(R) == 8 && im.max_depth <= RT_REC_DEPTH;
+    V3<R> att[RT_REC_DEPTH];                   // rec: the sample's attenuations, bounce by bounce
+    static_assert((feat_of<ACC>() & F_LIGHT) != 0, "a lit mode");
+    V3<R> dir[RT_REC_DEPTH];                   // rec: the bounces' direct terms
+    // dsum: the segment's (rec) or the sample's (forward) direct light
+    LightCtx<R> lc{mk<R>(0, 0, 0), &res.work, stk};
+    int nb = 0;
+    bool skip_tri = false;                     // tri_exit_bound (pt_core.h)
+    if (s < s_end) start_sample(sc, im, i, j, pkey, s, g, o, d);
+    while (s < s_end) {
+        const uint64_t t0 = RT_TICK();
+        const Closest<R> c = closest_hit_acc<R, ACC>(sc, o, d, res.work, stk, skip_tri);
+        const uint64_t t1 = RT_TICK();
+        if (RT_PROFILE) res.cyc[0] += t1 - t0;
+        ++res.segments;
+        V3<R> L;
+        if (rec) T = mk<R>(1, 1, 1);           // then T = 1 * attenuation and L = 1 * X: exact
+        const int depth0 = depth;
+        if (rec) lc.dsum = mk<R>(0, 0, 0);
+        const bool done = shade_segment<R, feat_of<ACC>(), ACC>(sc, c, o, d, T, depth, g, L, nullptr, &lc);
+        if (rec && done && depth != depth0) {       // the last allowed bounce scattered: direct + att * 0
+            att[nb] = T;
+            dir[nb++] = lc.dsum;
+        }
+        if (rec && !done) dir[nb] = lc.dsum;
+        if constexpr (sizeof(R) == 8 && (walk_of<ACC>() == ACC_BVH || walk_of<ACC>() == ACC_BVH_STACK || ACC == ACC_BVH_STACK_LEAN))
+            skip_tri = !done && c.kind == HIT_TRI && leaves_tri_hull(sc, c.idx, o, d);
+        const uint64_t t2 = RT_TICK();
+        if (RT_PROFILE) res.cyc[1] += t2 - t1;
+        if (rec && !done) att[nb++] = T;
+        if (done) {
+            if (rec) {
+                for (int k = nb - 1; k >= 0; --k)
+                    L = mk(dir[k].x + att[k].x * L.x, dir[k].y + att[k].y * L.y, dir[k].z + att[k].z * L.z);
+                nb = 0;
+            } else {
+                L = L + lc.dsum;
+                lc.dsum = mk<R>(0, 0, 0);
+            }
+            sx += (double)L.x; sy += (double)L.y; sz += (double)L.z;
+            if (COUNT) res.draws += g.k;
+            ++s;
+            T = mk<R>(1, 1, 1);
+            depth = im.max_depth;
+            if (s < s_end) start_sample(sc, im, i, j, pkey, s, g, o, d);
+        }
+        if (RT_PROFILE) res.cyc[2] += RT_TICK() - t2;
+    }
+    sum[0] = sx; sum[1] = sy; sum[2] = sz;
+    return res;
+}
+
 template <class R, bool COUNT, int ACC = ACC_BRUTE>
 RT_HD PixelResult trace_pixel(const SceneView<R>& sc, const ImageParams& im, int cx, int cy, int s_end, double* sum,
                               BvhStack stk = BvhStack{nullptr, 0}) {
+    // the lit modes: the twin above (this function's text is kept as it was, so that the kernels without
+    // F_LIGHT compile to what they were)
+    if constexpr ((feat_of<ACC>() & F_LIGHT) != 0) return trace_pixel_lit<R, COUNT, ACC>(sc, im, cx, cy, s_end, sum, stk);
+    else {
     const int i = im.x0 + cx, row = im.y0 + cy, j = im.height - 1 - row;
     const uint32_t pkey = pixel_key(im.seedm, (uint32_t)row * (uint32_t)im.width + (uint32_t)i);
     PixelResult res{0, 0, {0, 0, 0}, {0, 0, 0}};
@@ -366,6 +479,7 @@ RT_HD PixelResult trace_pixel(const SceneView<R>& sc, const ImageParams& im, int
     }
     sum[0] = sx; sum[1] = sy; sum[2] = sz;
     return res;
+    }
 }
 
 }  // namespace rt

@@ -348,6 +348,9 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
     size_t q = 0;
     Rng<R> g;
     V3<R> o, d, T;
+    constexpr bool LIT = (feat_of<ACC>() & F_LIGHT) != 0;
+    LightState<R, LIT> lc{mk<R>(0, 0, 0), &res.work, stk};   // LIT: dsum = the sample's direct light so far, sum of T (.) direct;
+                                                      // the shadow rays walk with the lane's own (idle) stack
     auto begin_item = [&](const uint32_t k) {
         uint32_t sr;
         if (nv == 64) { m = k & 63; sr = k >> 6; }
@@ -362,6 +365,7 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
         T = mk<R>(1, 1, 1);
         depth = im.max_depth;
         isegs = 0;
+        if constexpr (LIT) lc.dsum = mk<R>(0, 0, 0);
         start_sample<R, false, feat_of<ACC>()>(sc, im, i, j, pkey, s, g, o, d);
     };
     uint32_t next = 64;                       // items [0, 64) are dealt to lanes 0..63 up front
@@ -392,7 +396,12 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
             ++res.segments;
             ++isegs;
             V3<R> L;
-            waiting = shade_segment<R, feat_of<ACC>()>(sc, c, o, d, T, depth, g, L);
+            if constexpr (LIT) {
+                waiting = shade_segment<R, feat_of<ACC>(), ACC>(sc, c, o, d, T, depth, g, L, nullptr, &lc);
+                if (waiting) L = L + lc.dsum;
+            } else {
+                waiting = shade_segment<R, feat_of<ACC>()>(sc, c, o, d, T, depth, g, L);
+            }
             // the next segment leaves the triangle just hit away from every triangle: no triangle walk
             // (tri_exit_bound, pt_core.h; binary64 only)
             if constexpr (sizeof(R) == 8 && (walk_of<ACC>() == ACC_BVH || walk_of<ACC>() == ACC_BVH_STACK || ACC == ACC_BVH_STACK_LEAN))
@@ -860,6 +869,11 @@ RT_ONEWAVE_INST(double, ACC_BRUTE_TEX)
 RT_ONEWAVE_INST(double, ACC_BVH_STACK_TEX)
 RT_ONEWAVE_INST(float, ACC_BRUTE_TEX)
 RT_ONEWAVE_INST(float, ACC_BVH_STACK_TEX)
+// renders with direct lighting (scene lights): the same two walks, textures included
+RT_ONEWAVE_INST(double, ACC_BRUTE_LIT)
+RT_ONEWAVE_INST(double, ACC_BVH_STACK_LIT)
+RT_ONEWAVE_INST(float, ACC_BRUTE_LIT)
+RT_ONEWAVE_INST(float, ACC_BVH_STACK_LIT)
 #undef RT_ONEWAVE_INST
 #else   // !RT_ONEWAVE_TU: the rest of the file
 
@@ -1223,7 +1237,7 @@ static bool scene_lean(const SceneView<R>& sc, const ImageParams& im, int feat) 
         const char* e = getenv("RT_LEAN");
         return e ? atoi(e) : RT_LEAN;
     }();
-    if (v == 0 || (v == 2 && feat != 0) || sc.num_tex > 0) return false;   // (no lean kernel evaluates textures)
+    if (v == 0 || (v == 2 && feat != 0) || sc.num_tex > 0 || sc.num_lights > 0) return false;   // (no lean kernel evaluates textures or lights)
     return (sc.num_planes == 0 || (feat & F_PLANES)) && (sc.num_boxes == 0 || (feat & F_BOXES)) &&
            (sc.num_tri_nodes == 0 || (feat & F_TRIS)) && sc.background == 0 && !sc.cam_ortho && im.aa_mode == 0;
 }
@@ -1306,7 +1320,7 @@ static int bvh_walk_mode(const SceneView<R>& sc) {
 }
 
 template <class R>
-bool trace_walks_grid(const SceneView<R>& sc) { return sc.num_tex == 0 && bvh_walk_mode(sc) == ACC_GRID; }
+bool trace_walks_grid(const SceneView<R>& sc) { return sc.num_tex == 0 && sc.num_lights == 0 && bvh_walk_mode(sc) == ACC_GRID; }
 template bool trace_walks_grid<double>(const SceneView<double>&);
 template bool trace_walks_grid<float>(const SceneView<float>&);
 
@@ -1322,6 +1336,9 @@ hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Cou
     if (im.cw <= 0 || im.ch <= 0 || im.s_end <= im.s_begin) return hipSuccess;
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
+        return bvh ? launch_acc<R, ACC_BVH_STACK_LIT>(a, count, pool, stream)
+                   : launch_acc<R, ACC_BRUTE_LIT>(a, count, pool, stream);
     if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
         return bvh ? launch_acc<R, ACC_BVH_STACK_TEX>(a, count, pool, stream)
                    : launch_acc<R, ACC_BRUTE_TEX>(a, count, pool, stream);
@@ -1363,6 +1380,9 @@ hipError_t launch_trace_partials(const SceneView<R>& sc, const ImageParams& im, 
     if (!part || part_bytes < p.part_bytes) return hipErrorInvalidValue;
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
+        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_LIT>(a, count, p, part, stream)
+                   : launch_partials_acc<R, ACC_BRUTE_LIT>(a, count, p, part, stream);
     if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
         return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, p, part, stream)
                    : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, p, part, stream);
@@ -1404,6 +1424,9 @@ hipError_t launch_trace_batches(const SceneView<R>& sc, const ImageParams& im0, 
     const PoolPlan all{p.tiles, p.chunk, p.chunks * nb, (size_t)nb * p.part_bytes};
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
+        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_LIT>(a, count, all, part, stream)
+                   : launch_partials_acc<R, ACC_BRUTE_LIT>(a, count, all, part, stream);
     if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
         return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, all, part, stream)
                    : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, all, part, stream);
@@ -1445,6 +1468,9 @@ hipError_t launch_trace_bands(const SceneView<R>& sc, const ImageParams& im0, co
     im.band_chunks = p.chunks;
     TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
+    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
+        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_LIT>(a, count, p, part, stream)
+                   : launch_partials_acc<R, ACC_BRUTE_LIT>(a, count, p, part, stream);
     if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
         return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, p, part, stream)
                    : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, p, part, stream);
@@ -1565,7 +1591,7 @@ hipError_t launch_closest_hits(const SceneView<R>& sc, bool bvh, const double* r
                                int* idx, hipStream_t stream) {
     if (n == 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 63) / 64));
-    if (bvh && sc.num_tex > 0) {                                               // the walk the trace kernel runs
+    if (bvh && (sc.num_tex > 0 || sc.num_lights > 0)) {                        // the walk the trace kernel runs
         hipLaunchKernelGGL((closest_hits_kernel<R, ACC_BVH_STACK>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
         return hipGetLastError();
     }
@@ -1592,6 +1618,35 @@ template hipError_t launch_closest_hits<double>(const SceneView<double>&, bool, 
                                                 hipStream_t);
 template hipError_t launch_closest_hits<float>(const SceneView<float>&, bool, const double*, size_t, double*, int*, int*,
                                                hipStream_t);
+
+// ---- World.hit(ray, 0.001, tmax) !== null for given rays (rt_occluded: the lit kernels' any-hit query) ----
+template <class R, int ACC>
+__global__ __launch_bounds__(64) void occluded_kernel(const SceneView<R> sc, const double* __restrict__ rays,
+                                                      const double* __restrict__ tmax, const size_t n,
+                                                      uint8_t* __restrict__ out) {
+    __shared__ int stack[RT_BVH_STACK * 64];
+    const BvhStack stk{stack + threadIdx.x, 64};
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n) return;
+    const double* q = rays + 6 * r;
+    const V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), d = mk<R>((R)q[3], (R)q[4], (R)q[5]);
+    Work w{0, 0, 0, 0, 0, 0};
+    out[r] = occluded<R, ACC>(sc, o, d, (R)tmax[r], w, stk) ? 1 : 0;
+}
+
+template <class R>
+hipError_t launch_occluded(const SceneView<R>& sc, bool bvh, const double* rays, const double* tmax, size_t n,
+                           uint8_t* out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (bvh) hipLaunchKernelGGL((occluded_kernel<R, ACC_BVH_STACK_LIT>), grid, dim3(64), 0, stream, sc, rays, tmax, n, out);
+    else hipLaunchKernelGGL((occluded_kernel<R, ACC_BRUTE_LIT>), grid, dim3(64), 0, stream, sc, rays, tmax, n, out);
+    return hipGetLastError();
+}
+template hipError_t launch_occluded<double>(const SceneView<double>&, bool, const double*, const double*, size_t, uint8_t*,
+                                            hipStream_t);
+template hipError_t launch_occluded<float>(const SceneView<float>&, bool, const double*, const double*, size_t, uint8_t*,
+                                           hipStream_t);
 
 // ---- Texture.value at given points (rt_texture_values: texture_value, the trace kernels' function) ----
 template <class R>

@@ -110,6 +110,7 @@ struct DeviceScene {
     // them is uploaded behind the world's table in `perm` (pt_core.h tex_view)
     DevBuf<TexRec<R>> tex_recs;
     DevBuf<int> tex_perms, mat_tex;
+    DevBuf<LightRec<R>> light_recs;      // scene lights (lit scenes only): the LightView follows the TexView
     SceneView<R> view{};
     void release() {
         runs.release(); spheres.release(); sphere_filter.release(); sphere_r.release(); sphere_inv_r.release(); planes.release(); boxes.release(); tris.release();
@@ -117,7 +118,7 @@ struct DeviceScene {
         plane_obj.release(); box_obj.release(); sphere_nodes.release(); tri_nodes.release(); bvh_sphere_leaf.release();
         bvh_tri_leaf.release(); tri_filter.release(); tri_exit.release(); big_sphere_leaf.release();
         sphere_wide.release(); tri_wide.release(); grid_cell.release(); grid_leaf.release();
-        tex_recs.release(); tex_perms.release(); mat_tex.release();
+        tex_recs.release(); tex_perms.release(); mat_tex.release(); light_recs.release();
     }
 };
 
@@ -130,10 +131,15 @@ int build_device(DeviceScene<R>& ds, const HostScene& hs, const rt_scene_desc& d
     UP(runs, hs.runs); UP(spheres, rec.spheres); UP(sphere_filter, rec.sphere_filter); UP(sphere_r, rec.sphere_r); UP(sphere_inv_r, rec.sphere_inv_r); UP(planes, rec.planes);
     UP(boxes, rec.boxes); UP(tris, rec.tris); UP(sphere_mat, hs.sphere_mat); UP(plane_mat, hs.plane_mat);
     UP(box_mat, hs.box_mat); UP(tri_mat, hs.tri_mat); UP(mats, rec.mats);
-    const bool textured = !rec.tex_recs.empty();
-    if (textured) {          // the TexView over the uploaded arrays goes behind the world's table (tex_view)
+    const bool textured = !rec.tex_recs.empty(), lit = !rec.light_recs.empty();
+    if (textured || lit) {   // the TexView over the uploaded arrays goes behind the world's table (tex_view)
         UP(tex_recs, rec.tex_recs); UP(tex_perms, rec.tex_perms); UP(mat_tex, rec.mat_tex);
-        rec.set_tex_view(TexView<R>{ds.tex_recs.p, ds.tex_perms.p, ds.mat_tex.p, (int)rec.tex_recs.size(), d.num_texture_perms});
+        rec.set_tex_view(TexView<R>{ds.tex_recs.p, ds.tex_perms.p, ds.mat_tex.p, (int)rec.tex_recs.size(),
+                                    (int)(rec.tex_perms.size() / 512)});
+    }
+    if (lit) {               // ... and the LightView behind it (light_view)
+        UP(light_recs, rec.light_recs);
+        rec.set_light_view(LightView<R>{ds.light_recs.p, (int)rec.light_recs.size(), 0});
     }
     UP(perm, rec.perm);
     UP(plane_obj, hs.plane_obj); UP(box_obj, hs.box_obj); UP(sphere_nodes, hs.sphere_bvh); UP(tri_nodes, hs.tri_bvh);
@@ -277,8 +283,11 @@ struct DescCopy {
     std::vector<double> triangles;
     std::vector<rt_texture_desc> textures;
     std::vector<int32_t> material_texture, texture_perms;
+    std::vector<rt_light_desc> lights;
     void set(const rt_scene_desc& src) {
         d = src;
+        lights.assign(src.lights, src.lights + std::max(0, src.num_lights));
+        d.lights = lights.data();
         textures.assign(src.textures, src.textures + std::max(0, src.num_textures));
         if (src.material_texture) material_texture.assign(src.material_texture, src.material_texture + std::max(0, src.num_materials));
         texture_perms.assign(src.texture_perms, src.texture_perms + 512 * (size_t)std::max(0, src.num_texture_perms));
@@ -839,6 +848,7 @@ int rt_scene_create(const rt_scene_desc* caller_desc, int device, rt_scene** out
     {
         std::string terr;                      // host-only checks first: a bad descriptor is RT_ERR_INVALID
         if (!validate_textures(*desc, terr)) return fail(RT_ERR_INVALID, "%s", terr.c_str());   // with or without a device
+        if (!validate_lights(*desc, terr)) return fail(RT_ERR_INVALID, "%s", terr.c_str());
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_ERR_NO_DEVICE, "no HIP device visible");
@@ -1756,6 +1766,37 @@ int rt_closest_hits(rt_scene* sc, int32_t precision, int32_t accel, const double
     if (e == hipSuccess) e = es;
     cleanup();
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_closest_hits: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_occluded(rt_scene* sc, int32_t precision, int32_t accel, const double* rays, const double* tmax, size_t n,
+                uint8_t* out) {
+    if (!sc || (n > 0 && (!rays || !tmax || !out))) return fail(RT_ERR_INVALID, "NULL argument");
+    if (precision != RT_PREC_F64 && precision != RT_PREC_F32) return fail(RT_ERR_INVALID, "precision %d", precision);
+    rt_settings s{};
+    s.accel = accel;
+    if (s.accel < RT_ACCEL_AUTO || s.accel > RT_ACCEL_BVH) return fail(RT_ERR_INVALID, "accel %d", accel);
+    int rc = check_accel(sc, &s);
+    if (rc) return rc;
+    if (n == 0) return RT_OK;
+    DeviceState& ds = sc->home;
+    HIP_TRY(hipSetDevice(ds.device));
+    DevBuf<double> d_rays, d_tmax;
+    DevBuf<uint8_t> d_out;
+    hipError_t e = d_rays.ensure(6 * n);
+    if (e == hipSuccess) e = d_tmax.ensure(n);
+    if (e == hipSuccess) e = d_out.ensure(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays.p, rays, 6 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tmax.p, tmax, n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
+    const bool bvh = use_bvh(sc, &s);
+    if (e == hipSuccess)
+        e = precision == RT_PREC_F32 ? launch_occluded<float>(ds.s32.view, bvh, d_rays.p, d_tmax.p, n, d_out.p, ds.stream)
+                                     : launch_occluded<double>(ds.s64.view, bvh, d_rays.p, d_tmax.p, n, d_out.p, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, n, hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_rays.release(); d_tmax.release(); d_out.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_occluded: %s", hipGetErrorString(e));
     return RT_OK;
 }
 

@@ -4,7 +4,9 @@
 //                 [--aa supersampling|stochastic|none] [--tone reinhard|aces|linear]
 //                 [--exposure E] [--gamma G] [--denoise STRENGTH] [--precision f64|f32]
 //                 [--accel auto|bvh|brute] [--frames K] [--warmup W] [--batch B] [--device N]
-//                 [--out image.ppm|image.pam]
+//                 [--out image.ppm|image.pam] [--lights]
+//
+// --lights: direct lighting from the scene's "lights" (rt_json_scene_desc_lit; off by default)
 //
 // Does what a reference user does in the browser: RayTracer(width, height) -> loadFromJSON(scene)
 // (rt_json_scene_load: scene-loader.js semantics incl. a camera "resolution" resize) ->
@@ -58,7 +60,7 @@ int main(int argc, char** argv) {
     if (argc < 2 || !strcmp(argv[1], "--help")) {
         fprintf(stderr, "usage: rt_render_cli scene.json [--width W --height H --spp S --depth D --seed N --aa MODE "
                         "--tone MAP --exposure E --gamma G --denoise STRENGTH --precision f64|f32 --accel auto|bvh|brute "
-                        "--frames K --warmup W --batch B --device N --out FILE]\n");
+                        "--frames K --warmup W --batch B --device N --out FILE --lights]\n");
         return argc < 2 ? 2 : 0;
     }
     const char* scene_path = argv[1];
@@ -66,8 +68,10 @@ int main(int argc, char** argv) {
     double spp = 4, depth = 5, exposure = 1.0, gamma = 2.2, denoise = 0;
     uint32_t seed = 1;
     std::string aa = "supersampling", tone = "reinhard", precision = "f64", accel = "auto", out;
+    bool lights = false;
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
+        if (a == "--lights") { lights = true; continue; }
         if (i + 1 >= argc) die("missing value for ", a.c_str());
         const char* v = argv[++i];
         if (a == "--width") width = atoi(v);
@@ -97,7 +101,9 @@ int main(int argc, char** argv) {
     rt_json_scene_size(js, &width, &height);                 // a camera "resolution" resizes
     rt_scene* scene = nullptr;
     const double t_up = now_ms();
-    check(rt_scene_create(rt_json_scene_desc(js), device, &scene), "uploading the scene");
+    const rt_scene_desc* desc = lights ? rt_json_scene_desc_lit(js) : rt_json_scene_desc(js);
+    if (!desc) die("--lights: ", rt_last_error());
+    check(rt_scene_create(desc, device, &scene), "uploading the scene");
     const double upload_ms = now_ms() - t_up;
 
     rt_settings s{};

@@ -320,8 +320,9 @@ struct rt_json_scene {
     // 512 entries per noise-bearing texture
     std::vector<rt_texture_desc> textures;
     std::vector<int32_t> material_texture, texture_perms;
+    std::vector<rt_light_desc> lights;       // World.lights (desc_lit points into it; desc ignores it)
     uint32_t seed = 0;
-    rt_scene_desc desc{};
+    rt_scene_desc desc{}, desc_lit{};
     int32_t width = 0, height = 0;
 };
 
@@ -580,13 +581,26 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
                 if (o.t == JVal::Null) throw LoadError{"object is null"};   // objData.type on null throws
                 create_object(*s, o);
             }
-        // lights (scene-loader.js:69-76) are parsed but never rendered; _createLight calls
-        // lightData.type.toLowerCase() (:187), which throws for a truthy non-string type: the load fails
+        // lights (scene-loader.js:69-76, 179-200); _createLight calls lightData.type.toLowerCase() (:187),
+        // which throws for a truthy non-string type: the load fails
         const JVal* lights = root.get("lights");
         if (truthy(lights) && lights->t == JVal::Arr)
             for (const JVal& l : lights->a) {
                 const JVal* lt = l.t == JVal::Obj ? l.get("type") : nullptr;
-                if (truthy(lt) && lt->t != JVal::Str) throw LoadError{"light.type is not a string"};
+                if (!truthy(lt)) continue;
+                const std::string ty = type_of(lt, "light");
+                const JVal* col = l.get("color");
+                const V color = truthy(col) ? parse_vec3(col) : V{1, 1, 1};          // lightData.color || [1, 1, 1]
+                const JVal* in = l.get("intensity");
+                rt_light_desc ld{};
+                ld.intensity = in ? num(in) : 1.0;                                   // !== undefined
+                ld.color[0] = color.x; ld.color[1] = color.y; ld.color[2] = color.z;
+                V v;
+                if (ty == "point") { ld.type = RT_LIGHT_POINT; v = parse_vec3(l.get("position")); }
+                else if (ty == "directional") { ld.type = RT_LIGHT_DIRECTIONAL; v = vnorm(parse_vec3(l.get("direction"))); }   // lights.js:38
+                else continue;                                                       // unknown type: skipped
+                ld.v[0] = v.x; ld.v[1] = v.y; ld.v[2] = v.z;
+                s->lights.push_back(ld);
             }
         Camera c;
         if (truthy(cam)) {
@@ -615,6 +629,15 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
         d.material_texture = s->material_texture.data();
         d.num_texture_perms = (int32_t)(s->texture_perms.size() / 512);
         d.texture_perms = s->texture_perms.data();
+        // the same scene with its lights (rt_json_scene_desc_lit); without lights it is the unlit descriptor.
+        // More than RT_MAX_LIGHTS lights load like any others (the reference's loader has no limit): only
+        // asking for the lit descriptor is refused, as the Python and JS hosts refuse to pack them
+        s->desc_lit = d;
+        if (!s->lights.empty()) {
+            s->desc_lit.extensions = RT_DESC_LIGHTS;
+            s->desc_lit.num_lights = (int32_t)s->lights.size();
+            s->desc_lit.lights = s->lights.data();
+        }
     } catch (const LoadError& e) {
         return rt::set_error(RT_ERR_INVALID, e.msg.c_str());
     } catch (const std::bad_alloc&) {
@@ -625,6 +648,14 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
 }
 
 const rt_scene_desc* rt_json_scene_desc(const rt_json_scene* scene) { return scene ? &scene->desc : nullptr; }
+const rt_scene_desc* rt_json_scene_desc_lit(const rt_json_scene* scene) {
+    if (!scene) return nullptr;
+    if (scene->lights.size() > RT_MAX_LIGHTS) {
+        rt::set_error(RT_ERR_INVALID, "more than RT_MAX_LIGHTS lights");
+        return nullptr;
+    }
+    return &scene->desc_lit;
+}
 
 void rt_json_scene_size(const rt_json_scene* scene, int32_t* width, int32_t* height) {
     if (!scene) return;

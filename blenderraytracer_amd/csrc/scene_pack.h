@@ -130,7 +130,21 @@ inline bool pack_host(const rt_scene_desc& d, HostScene& hs, std::string& err) {
 inline bool desc_as_filled(const rt_scene_desc* d, rt_scene_desc& out) {
     if (d->abi_version != RT_ABI_VERSION) return false;
     memset(&out, 0, sizeof out);
-    memcpy(&out, d, d->extensions == RT_DESC_TEXTURES ? sizeof out : offsetof(rt_scene_desc, num_textures));
+    memcpy(&out, d, d->extensions == RT_DESC_LIGHTS ? sizeof out
+                  : d->extensions == RT_DESC_TEXTURES ? offsetof(rt_scene_desc, num_lights)
+                  : offsetof(rt_scene_desc, num_textures));
+    return true;
+}
+// The light part of the descriptor (extensions == RT_DESC_LIGHTS; zero otherwise), checked on the host before
+// anything is uploaded
+inline bool validate_lights(const rt_scene_desc& d, std::string& err) {
+    char buf[256];
+    auto bad = [&](const char* fmt, int a, int b) { snprintf(buf, sizeof buf, fmt, a, b); err = buf; return false; };
+    if (d.num_lights < 0 || d.num_lights > RT_MAX_LIGHTS) return bad("num_lights %d (0 .. %d)", d.num_lights, RT_MAX_LIGHTS);
+    if (d.num_lights > 0 && !d.lights) return bad("lights is NULL with num_lights %d", d.num_lights, 0);
+    for (int i = 0; i < d.num_lights; ++i)
+        if (d.lights[i].type < RT_LIGHT_POINT || d.lights[i].type > RT_LIGHT_DIRECTIONAL)
+            return bad("light %d: type %d", i, d.lights[i].type);
     return true;
 }
 
@@ -709,8 +723,16 @@ struct HostRecords {
     std::vector<int> tex_perms, mat_tex;
     void set_tex_view(const TexView<R>& tv) {
         static_assert(sizeof(TexView<R>) % sizeof(int) == 0, "TexView in ints");
-        perm.resize(kTexViewAt + sizeof(TexView<R>) / sizeof(int));
+        perm.resize(std::max(perm.size(), kTexViewAt + sizeof(TexView<R>) / sizeof(int)));
         memcpy(perm.data() + kTexViewAt, &tv, sizeof tv);
+    }
+    // scene lights (empty unless the descriptor carries lights): a lit scene has mat_tex (all -1 without
+    // textures) and a TexView too, and its LightView behind that (light_view)
+    std::vector<LightRec<R>> light_recs;
+    void set_light_view(const LightView<R>& lv) {
+        static_assert(sizeof(LightView<R>) % sizeof(int) == 0, "LightView in ints");
+        perm.resize(std::max(perm.size(), kLightViewAt + sizeof(LightView<R>) / sizeof(int)));
+        memcpy(perm.data() + kLightViewAt, &lv, sizeof lv);
     }
     // BVH leaf-order records (bvh_sphere_leaf[k] describes spheres[bvh_sphere_leaf[k].id], same for
     // triangles)
@@ -792,6 +814,18 @@ void make_records(const HostScene& hs, const rt_scene_desc& d, HostRecords<R>& o
         out.tex_perms.assign(d.texture_perms, d.texture_perms + 512 * (size_t)d.num_texture_perms);
         out.mat_tex.assign(d.material_texture, d.material_texture + d.num_materials);
     }
+    if (d.num_lights > 0) {
+        if (out.mat_tex.empty()) out.mat_tex.assign((size_t)std::max(1, d.num_materials), -1);
+        out.light_recs.resize(d.num_lights);
+        for (int i = 0; i < d.num_lights; ++i) {
+            const rt_light_desc& l = d.lights[i];
+            LightRec<R> r{};
+            r.type = l.type;
+            for (int k = 0; k < 3; ++k) { r.v[k] = (R)l.v[k]; r.color[k] = (R)l.color[k]; }
+            r.intensity = (R)l.intensity;
+            out.light_recs[i] = r;
+        }
+    }
     auto leaf = [&](int id) {
         SphereLeaf<R> L{};
         if constexpr (sizeof(R) == 8) L.f = out.sphere_filter[id];
@@ -821,6 +855,7 @@ void fill_view_constants(SceneView<R>& v, const HostScene& hs, const rt_scene_de
     v.num_planes = (int)hs.plane_mat.size();
     v.num_mats = d.num_materials;
     v.num_tex = scene_textured(d) ? d.num_textures : 0;
+    v.num_lights = d.num_lights;
     v.num_boxes = (int)hs.box_mat.size();
     v.num_sphere_nodes = (int)hs.sphere_bvh.size();
     v.num_tri_nodes = (int)hs.tri_bvh.size();
@@ -889,9 +924,10 @@ inline SceneView<double> host_view(const HostScene& hs, const rt_scene_desc& d, 
     v.big_spheres = rec.big_sphere_leaf.data();
     v.sphere_wide = hs.sphere_wide.data(); v.tri_wide = hs.tri_wide.data();
     v.grid_cell = hs.grid_cell.data(); v.grid_leaf = rec.grid_leaf.data();
-    if (!rec.tex_recs.empty()) {
+    if (!rec.tex_recs.empty() || !rec.light_recs.empty()) {
         rec.set_tex_view(TexView<double>{rec.tex_recs.data(), rec.tex_perms.data(), rec.mat_tex.data(),
-                                         (int)rec.tex_recs.size(), d.num_texture_perms});
+                                         (int)rec.tex_recs.size(), (int)(rec.tex_perms.size() / 512)});
+        if (!rec.light_recs.empty()) rec.set_light_view(LightView<double>{rec.light_recs.data(), (int)rec.light_recs.size(), 0});
         v.perm = rec.perm.data();
     }
     fill_view_constants(v, hs, d);

@@ -89,14 +89,16 @@ function samePacked(a, b) {
     if (!a || !b) return false;
     for (const k of ['objects', 'materials', 'triangles', 'camera', 'solidColor', 'perm', 'textures', 'materialTexture', 'texturePerms'])
         if (!bytesOf(a[k]).equals(bytesOf(b[k]))) return false;
+    if ((a.lights === undefined) !== (b.lights === undefined)) return false;
+    if (a.lights && !bytesOf(a.lights).equals(bytesOf(b.lights))) return false;
     return a.cameraType === b.cameraType && a.background === b.background && Object.is(a.skyIntensity, b.skyIntensity);
 }
 
 // The scene resident on the GPU for this RayTracer: packed from world / camera at every render (cheap)
 // and compared byte for byte with the cached one, so the upload and the BVH build happen only when
 // the scene or the camera changed (presets, loadFromJSON, updateCamera, updateBackground...).
-function residentScene(rt, nat, device) {
-    const packed = packScene(rt.world, rt.camera);
+function residentScene(rt, nat, device, lights) {
+    const packed = packScene(rt.world, rt.camera, lights ? { lights: true } : {});
     const c = rt.__gpuScene;
     if (c && c.device === device && samePacked(c.packed, packed)) return c.scene;
     if (c) nat.destroyScene(c.scene);
@@ -136,7 +138,10 @@ function lazyCheckpoint(rt, nat, scene, samplesDone) {
 // cancelled, like the reference which then stops silently, ray-tracer.js:256,264).
 export async function gpuRender(rt, onProgress, opts = {}) {
     const nat = loadNative();
-    const scene = residentScene(rt, nat, opts.device || 0);
+    // direct lighting (opt-in): the RayTracer's own directLighting member (GpuRayTracer), else the option
+    // (installGpuRender on a reference RayTracer, which has no such member)
+    const lit = rt.directLighting !== undefined ? !!rt.directLighting : !!opts.directLighting;
+    const scene = residentScene(rt, nat, opts.device || 0, lit);
     // a resident checkpoint is resumed from the device (decided before this render supersedes it)
     const resume = opts.resume && opts.resume.resident ? { resident: true, samplesDone: opts.resume.samplesDone }
         : opts.resume ? { sums: opts.resume.sums, samplesDone: opts.resume.samplesDone } : undefined;
@@ -178,6 +183,7 @@ function blit(rt, res) {
 // Option 1: swap the render() of a reference RayTracer instance for the GPU path.
 // opts: {seed, precision: 'f64'|'f32', accel, batchSamples | progressSteps (default 16), device,
 //        devices: [HIP ordinals], sumOrder: 'pool' | 'sample',
+//        directLighting: render this.world.lights (the reference's own PointLight / DirectionalLight objects),
 //        keepFloatData: also read back the post-gamma Float32 frame into this.floatData}
 export function installGpuRender(rayTracer, opts = {}) {
     rayTracer.render = async function render(onProgress) {
@@ -202,6 +208,7 @@ export class GpuRayTracer {
         this.maxBounces = 5; this.samples = 4; this.gamma = 2.2; this.exposure = 1.0;
         this.toneMapping = 'reinhard'; this.antiAliasing = 'supersampling';
         this.denoising = false; this.denoiseStrength = 0.5;
+        this.directLighting = !!opts.directLighting;                // opt-in: render world.lights
         const d = defaultScene(this.width, this.height, permutation(opts.seed || 0));
         this.world = d.world;
         this.camera = d.camera;
@@ -236,6 +243,7 @@ export class GpuRayTracer {
         this.antiAliasing = p.antiAliasing || 'supersampling';
         this.denoising = p.denoising || false;
         this.denoiseStrength = p.denoiseStrength || 0.5;
+        if (p.directLighting !== undefined) this.directLighting = !!p.directLighting;   // (not a reference setting)
     }
 
     updateBackground(type, intensity = 1.0) {                        // ray-tracer.js:568-585

@@ -10,6 +10,8 @@ export const BG_CODE = { gradient: 0, solid: 1, hdri: 2, procedural_sky: 3, nan:
 export const OBJECT_BYTES = 64;
 export const MATERIAL_BYTES = 72;
 export const TEXTURE_BYTES = 64;
+export const LIGHT_BYTES = 64;
+export const MAX_LIGHTS = 32;
 export const TEX = { checker: 0, noise: 1, marble: 2, wood: 3 };
 
 // A texture object of TexturedLambertian / TexturedMetal (materials.js:99-126), duck-typed on the reference's
@@ -90,7 +92,26 @@ function triangleRecord(t, out, k) {
     out[b + 9] = n.x; out[b + 10] = n.y; out[b + 11] = n.z;
 }
 
-export function packScene(world, camera) {
+// rt_light_desc records of world.lights (lights.js), duck-typed: a DirectionalLight has `direction` (already
+// normalized by its constructor), a PointLight only `position`
+function lightRecords(lights) {
+    if (lights.length > MAX_LIGHTS) throw new Error(`at most ${MAX_LIGHTS} lights`);
+    const buf = new ArrayBuffer(LIGHT_BYTES * lights.length);
+    const li = new Int32Array(buf), lf = new Float64Array(buf);
+    lights.forEach((l, i) => {
+        const b = i * (LIGHT_BYTES / 8);
+        const dirl = l.direction !== undefined;
+        const v = dirl ? l.direction : l.position;
+        li[2 * b] = dirl ? 1 : 0;
+        lf[b + 1] = v.x; lf[b + 2] = v.y; lf[b + 3] = v.z;
+        lf[b + 4] = l.color.x; lf[b + 5] = l.color.y; lf[b + 6] = l.color.z;
+        lf[b + 7] = l.intensity;
+    });
+    return new Uint8Array(buf);
+}
+
+// opts.lights: also pack world.lights (direct lighting) as `lights`; without it the result is the unlit scene's
+export function packScene(world, camera, opts = {}) {
     const mats = [];
     const matIndex = new Map();
     const texs = [], texIndex = new Map(), texPerms = [];
@@ -193,5 +214,6 @@ export function packScene(world, camera) {
         textures: new Uint8Array(textures),
         materialTexture,
         texturePerms,
+        ...(opts.lights ? { lights: lightRecords(world.lights || []) } : {}),
     };
 }

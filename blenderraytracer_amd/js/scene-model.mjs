@@ -6,6 +6,7 @@
 //   Plane / Triangle / Mesh    js/geometry.js:50-53, 140-146, 193-237
 //   materials                  js/materials.js:14-126
 //   textures                   js/textures.js:9-81 (fields only: the values are computed on the GPU)
+//   lights                     js/lights.js:8-48 (fields only: illuminate runs on the GPU)
 //   World + backgrounds        js/world.js:8-16 (background kinds are tagged, see backgroundKind)
 //   SceneLoader.loadFromJSON   js/scene-loader.js:20-284
 import { permutation, texturePermutation } from './keyed-rng.mjs';
@@ -69,6 +70,16 @@ export class WoodTexture { constructor(perm, scale = 1) { this.scale = scale; th
 export class TexturedLambertian { constructor(texture) { this.texture = texture; } }
 export class TexturedMetal { constructor(texture, roughness = 0) { this.texture = texture; this.roughness = Math.min(roughness, 1); } }
 
+// lights: same fields as the reference classes (lights.js:8-48); the directional light's constructor normalizes
+// its direction (a zero vector stays zero)
+export class PointLight { constructor(position, color, intensity = 1) { this.position = position; this.color = color; this.intensity = intensity; } }
+export class DirectionalLight {
+    constructor(direction, color, intensity = 1) {
+        this.position = new Vec3(); this.color = color; this.intensity = intensity;
+        this.direction = direction.normalize();
+    }
+}
+
 // geometry: same fields as the reference classes
 export class Sphere { constructor(center, radius, material) { this.center = center; this.radius = radius; this.material = material; } }
 export class Plane { constructor(point, normal, material) { this.point = point; this.normal = normal.normalize(); this.material = material; } }
@@ -105,6 +116,7 @@ export class World {
         this.cloudNoise = { p: perm };
     }
     add(o) { this.objects.push(o); }
+    addLight(l) { this.lights.push(l); }
 }
 
 const parseVec3 = (a) => (Array.isArray(a) && a.length >= 3 ? new Vec3(a[0], a[1], a[2]) : new Vec3(0, 0, 0));
@@ -143,6 +155,17 @@ function createMaterial(m, tp) {
         case 'dielectric': return new Dielectric(m.ior !== undefined ? m.ior : 1.5);
         case 'emissive': return new Emissive(parseVec3(m.color), m.intensity !== undefined ? m.intensity : 1.0);
         default: return new Lambertian(new Vec3(0.8, 0.8, 0.8));
+    }
+}
+
+function createLight(l) {                                           // scene-loader.js:179-200
+    if (!l || !l.type) return null;
+    const color = parseVec3(l.color || [1, 1, 1]);
+    const intensity = l.intensity !== undefined ? l.intensity : 1.0;
+    switch (l.type.toLowerCase()) {                                 // throws for a truthy non-string type: the load fails
+        case 'point': return new PointLight(parseVec3(l.position), color, intensity);
+        case 'directional': return new DirectionalLight(parseVec3(l.direction), color, intensity);
+        default: return null;
     }
 }
 
@@ -201,10 +224,9 @@ export function loadFromJSON(json, width, height, perm, texturePerm) {
     }
     const tp = texturePerm ? { next: 0, perm: texturePerm } : null;
     if (Array.isArray(json.objects)) for (const o of json.objects) { const obj = createObject(o, tp); if (obj) world.add(obj); }
-    // lights (scene-loader.js:69-76) are parsed but never rendered; _createLight calls
-    // lightData.type.toLowerCase() (:187), which throws for a truthy non-string type: the load fails
+    // lights (scene-loader.js:69-76): kept in world.lights; rendered only with directLighting (pack.mjs)
     if (json.lights && Array.isArray(json.lights))
-        for (const l of json.lights) if (l && l.type) l.type.toLowerCase();
+        for (const l of json.lights) { const light = createLight(l); if (light) world.addLight(light); }
     const camera = json.camera ? createCamera(json.camera, width / height) : null;
     return { world, camera, newDimensions };
 }

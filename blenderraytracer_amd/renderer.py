@@ -54,8 +54,9 @@ def settings_struct(width, height, samples, max_bounces, anti_aliasing, tone_map
 
 class GpuRayTracer:
     def __init__(self, width, height, seed=0, device=0, precision=capi.RT_PREC_F64, accel=capi.RT_ACCEL_AUTO,
-                 sum_order=capi.RT_SUM_POOL):
+                 sum_order=capi.RT_SUM_POOL, direct_lighting=False):
         self.width, self.height = int(width), int(height)
+        self.direct_lighting = bool(direct_lighting)   # opt-in: render World.lights
         self.seed = seed
         self.device = device
         self.precision = precision
@@ -104,6 +105,9 @@ class GpuRayTracer:
         self.anti_aliasing = js_or(g("antiAliasing"), "supersampling")
         self.denoising = js_or(g("denoising"), False)
         self.denoise_strength = js_or(g("denoiseStrength"), 0.5)
+        if "directLighting" in params and bool(truthy(g("directLighting"))) != self.direct_lighting:
+            self.direct_lighting = not self.direct_lighting
+            self._dirty = True                      # the lights are part of the scene on the device
 
     def update_background(self, type, intensity=1.0):
         self.world.sky_intensity = intensity
@@ -115,7 +119,7 @@ class GpuRayTracer:
     # ---- packing / rendering --------------------------------------------------------------------
     def packed(self):
         if self._dirty or self._packed is None:
-            self._packed = PackedScene(self.world, self.camera)
+            self._packed = PackedScene(self.world, self.camera, lights=self.direct_lighting)
         return self._packed
 
     def settings(self, crop=None, sample_range=None, batch_samples=0, devices=None):

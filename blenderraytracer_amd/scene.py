@@ -7,7 +7,8 @@ never fused):
   Plane normal / Triangle normal / TriangleMesh construction                  js/geometry.js:50-53,140-146,193-237
   RayTracer default scene, setupCamera (resize), updateBackground             js/ray-tracer.js:42-77,439-474,568-585
 The packed form is include/rt_hip.h's rt_scene_desc (objects in World.objects insertion order).
-Lights are parsed by the reference but never used by the renderer, so they are dropped.
+Lights are parsed by the reference but never used by its renderer: World.lights keeps them, and
+PackedScene packs them only when asked to (lights=True, direct lighting: INTEGRATION.md).
 """
 import ctypes as C
 import json
@@ -167,6 +168,12 @@ class World:
         # one's table is texture_perm(k) (rng.texture_permutation under the render seed)
         self.texture_perm = texture_perm
         self.texture_perms = []
+        # World.lights (world.js addLight) in scene order: ("point", position, color, intensity) /
+        # ("directional", normalized direction, color, intensity)
+        self.lights = []
+
+    def add_light(self, light):
+        self.lights.append(light)
 
     def new_texture_perm(self):
         if self.texture_perm is None:
@@ -280,15 +287,29 @@ def load_from_json(data, width, height, perm, texture_perm=None):
     if isinstance(objs, list):
         for o in objs:
             _create_object(o, world)
-    # lights (scene-loader.js:69-76) are parsed but never rendered; _createLight calls
-    # lightData.type.toLowerCase() (:187), which throws for a truthy non-string type: the load fails
+    # lights (scene-loader.js:69-76, 179-200); _createLight calls lightData.type.toLowerCase() (:187), which
+    # throws for a truthy non-string type: the load fails
     lights = data.get("lights")
     if isinstance(lights, list):
         for lt in lights:
-            if isinstance(lt, dict) and truthy(lt.get("type")):
-                _js_lower(lt["type"], "light")
+            light = _create_light(lt)
+            if light is not None:
+                world.add_light(light)
     camera = create_camera(cam, width / height) if truthy(cam) else None
     return world, camera, new_dims
+
+
+def _create_light(lt):  # scene-loader.js:179-200 + the lights.js constructors
+    if not isinstance(lt, dict) or not truthy(lt.get("type")):
+        return None
+    color = parse_vec3(js_or(lt.get("color"), [1, 1, 1]))
+    intensity = num(lt["intensity"]) if "intensity" in lt else 1.0
+    t = _js_lower(lt["type"], "light")
+    if t == "point":
+        return ("point", parse_vec3(lt.get("position")), color, intensity)
+    if t == "directional":
+        return ("directional", vnorm(parse_vec3(lt.get("direction"))), color, intensity)   # lights.js:38
+    return None
 
 
 def default_scene(width, height, perm):
@@ -331,7 +352,9 @@ RECORD_BYTES = {"sphere": 16, "plane": 24, "box": 24, "triangle": 36}
 class PackedScene:
     """Owns the arrays an rt_scene_desc points into (keep it alive while the desc is used)."""
 
-    def __init__(self, world, camera):
+    def __init__(self, world, camera, lights=False):
+        """lights: pack World.lights too (direct lighting).  Only then, and only with at least one light, does the
+        descriptor carry RT_DESC_LIGHTS; otherwise it is exactly the unlit one."""
         mats, mat_index = [], {}
         objs = []
         tris = []
@@ -420,6 +443,20 @@ class PackedScene:
         d.textures = self.textures
         d.material_texture = self.material_texture.ctypes.data_as(C.POINTER(C.c_int32))
         d.texture_perms = self.texture_perms.ctypes.data_as(C.POINTER(C.c_int32))
+        # scene lights (the fields appended behind the texture fields): only on request
+        wl = list(getattr(world, "lights", [])) if lights else []
+        self.num_lights = len(wl)
+        if wl:
+            if len(wl) > capi.RT_MAX_LIGHTS:
+                raise ValueError(f"at most {capi.RT_MAX_LIGHTS} lights")
+            self.lights = (capi.LightDesc * len(wl))()
+            for i, (kind, v, color, intensity) in enumerate(wl):
+                ld = self.lights[i]
+                ld.type = capi.RT_LIGHT_POINT if kind == "point" else capi.RT_LIGHT_DIRECTIONAL
+                ld.v[:], ld.color[:], ld.intensity = v, color, intensity
+            d.extensions = capi.RT_DESC_LIGHTS
+            d.num_lights = self.num_lights
+            d.lights = self.lights
 
     def record_bytes_per_segment(self):
         """Σ canonical record bytes over every primitive one world.hit call tests."""

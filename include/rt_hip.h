@@ -37,6 +37,13 @@ extern "C" {
  * RT_DESC_TEXTURES; with any other value there the library reads nothing behind `perm`, so a binary built
  * against the shorter struct stays valid.  rt_texture_desc and rt_texture_values come with it. */
 #define RT_DESC_TEXTURES 0x54455834   /* "TEX4" */
+/* Scene lights (direct lighting) extend the descriptor once more, the same way: RT_DESC_LIGHTS in
+ * rt_scene_desc.extensions says that the texture fields AND the light fields appended behind them are filled.
+ * RT_DESC_TEXTURES keeps its meaning (nothing behind `texture_perms` is read); every other value still means
+ * the struct ends at `perm`.  rt_light_desc and rt_occluded come with it.  A scene created with at least one
+ * light renders with direct lighting; the hosts pass lights only when asked to. */
+#define RT_DESC_LIGHTS 0x4C495434     /* "LIT4" */
+#define RT_MAX_LIGHTS 32
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -136,6 +143,17 @@ typedef struct rt_texture_desc {
     double even[3];        /* CHECKER: colour elsewhere (a NaN product included) */
 } rt_texture_desc;         /* 64 bytes */
 
+/* lights.js:17-48.  Point: attenuation 1 / (1 + 0.1 d + 0.01 d^2), hard shadows.  Directional: v is the
+ * direction as the constructor normalized it (a zero vector stays zero: such a light never contributes). */
+typedef enum rt_light_type { RT_LIGHT_POINT = 0, RT_LIGHT_DIRECTIONAL = 1 } rt_light_type;
+typedef struct rt_light_desc {
+    int32_t type;          /* rt_light_type */
+    int32_t _pad;
+    double v[3];           /* POINT: position; DIRECTIONAL: normalized direction */
+    double color[3];
+    double intensity;
+} rt_light_desc;           /* 64 bytes */
+
 typedef struct rt_camera_desc {  /* vectors exactly as js/camera.js:8-36 computes them */
     double origin[3];
     double lower_left[3];
@@ -158,8 +176,9 @@ typedef struct rt_scene_desc {
                                             normalize(cross(v1-v0, v2-v0)) (geometry.js:143-145) */
     rt_camera_desc camera;
     int32_t background;                  /* rt_background_type */
-    int32_t extensions;                  /* RT_DESC_TEXTURES: the fields behind `perm` are filled; anything else
-                                            (it was padding): they are not read */
+    int32_t extensions;                  /* RT_DESC_TEXTURES: the texture fields behind `perm` are filled;
+                                            RT_DESC_LIGHTS: those and the light fields behind them; anything
+                                            else (it was padding): nothing behind `perm` is read */
     double sky_intensity;                /* World.skyIntensity */
     double solid_color[3];               /* RT_BG_SOLID color (updateBackground uses 0.1,0.1,0.1) */
     int32_t perm[512];                   /* World.cloudNoise.p (noise.js:6-18) */
@@ -174,6 +193,12 @@ typedef struct rt_scene_desc {
                                             NULL when num_textures == 0 */
     const int32_t* texture_perms;        /* num_texture_perms x 512: each noise-bearing texture's own
                                             PerlinNoise.p, entries in 0..255 */
+    /* extensions == RT_DESC_LIGHTS only (appended behind the texture fields, which are then read too).  With
+     * num_lights > 0 every Lambertian / textured Lambertian hit adds, per light in this order, its unoccluded
+     * (attenuation * light colour) * cos; no random number is drawn and no path decision changes. */
+    int32_t num_lights;                  /* 0 .. RT_MAX_LIGHTS */
+    int32_t _pad2;
+    const rt_light_desc* lights;         /* num_lights records, World.lights order */
 } rt_scene_desc;
 
 typedef struct rt_settings {
@@ -259,6 +284,11 @@ typedef struct rt_stats {
     uint64_t node_visits;        /* BVH nodes visited (0 for brute force) */
     uint64_t sphere_tests;       /* BVH: sphere / triangle tests in visited leaves (0 for brute force) */
     uint64_t tri_tests;
+    /* Direct lighting: shadow rays are not segments and draw nothing, so `segments` (and the per-pixel
+     * segments / draws outputs) of a lit render equal the unlit render's, and prim_tests / algorithmic_bytes
+     * of a brute-force render, which derive from segments, do not count shadow-ray work.  In BVH mode
+     * node_visits, sphere_tests and tri_tests (hence prim_tests and algorithmic_bytes there) include the
+     * shadow rays' walks. */
 } rt_stats;
 
 typedef struct rt_scene rt_scene;   /* opaque: scene resident in HBM of one device */
@@ -350,6 +380,13 @@ int rt_finalize_device(rt_scene* scene, const rt_settings* settings, const doubl
 int rt_closest_hits(rt_scene* scene, int32_t precision, int32_t accel, const double* rays, size_t n,
                     double* t, int32_t* kind, int32_t* index);
 
+/* Diagnostic (tests): the lit trace kernels' occlusion (any-hit) query, World.hit(ray, 0.001, tmax[i]) !== null,
+ * for `n` rays on the scene's device, the diagnostic twin of rt_closest_hits (same rays layout, precision and
+ * accel; any scene, lit or not).  out: host, n bytes, 1 = occluded.  A primitive at t == tmax does not occlude;
+ * tmax may be +inf. */
+int rt_occluded(rt_scene* scene, int32_t precision, int32_t accel, const double* rays, const double* tmax, size_t n,
+                uint8_t* out);
+
 /* Diagnostic (tests): Texture.value(u, v, p) of texture `texture` at `n` host points (n x 3 doubles; rounded
  * to binary32 first in RT_PREC_F32) evaluated on the scene's device by the function the trace kernels call;
  * rgb: host, n x 3 doubles.  RT_ERR_INVALID unless 0 <= texture < num_textures. */
@@ -358,8 +395,8 @@ int rt_texture_values(rt_scene* scene, int32_t precision, int32_t texture, const
 
 /* Diagnostic: the walk a render with these precision / accel settings runs on this scene — 0 World.objects
  * order (brute force), 1 a BVH tree walk, 2 the uniform grid over the spheres (sphere-only scenes where
- * the host's sampled cost estimate prefers it, scene_pack.h choose_walk; never for a scene with textures,
- * whose kernels walk World order or the trees); < 0 an error status.  Every walk finds the same closest
+ * the host's sampled cost estimate prefers it, scene_pack.h choose_walk; never for a scene with textures
+ * or lights, whose kernels walk World order or the trees); < 0 an error status.  Every walk finds the same closest
  * hit; they differ in speed only. */
 int rt_scene_walk(rt_scene* scene, int32_t precision, int32_t accel);
 

@@ -11,7 +11,8 @@
  * and packs the result into the rt_scene_desc of rt_hip.h, with the same JavaScript value
  * semantics (`||` defaults, `!== undefined` defaults, ToNumber of null/booleans, Math.min on the
  * metal roughness, Plane normal normalization, TriangleMesh index validation).  Lights are parsed by
- * the reference but never used by render(), so they are ignored.  Without a "camera" entry the
+ * the reference but never used by its render(): rt_json_scene_desc leaves them out, and
+ * rt_json_scene_desc_lit attaches them (direct lighting, opt-in).  Without a "camera" entry the
  * RayTracer keeps its constructor camera (ray-tracer.js:42-77: (3,2,2) -> (0,0,-1), fov 45,
  * aspect W/H, aperture 0, focus 10), which is what the loader returns then.
  * Like the reference's loadFromJSON (which catches and returns false), malformed input returns
@@ -36,6 +37,12 @@ int rt_json_scene_load(const char* json, size_t len, int32_t width, int32_t heig
 
 /* The packed scene, valid until rt_json_scene_destroy. */
 const rt_scene_desc* rt_json_scene_desc(const rt_json_scene* scene);
+
+/* The same scene with the parsed lights attached (scene-loader.js:179-200) and RT_DESC_LIGHTS set: a scene
+ * created from it renders with direct lighting.  Without lights it equals rt_json_scene_desc's descriptor.
+ * A scene with more than RT_MAX_LIGHTS lights loads (rt_json_scene_desc is unaffected), but has no lit
+ * descriptor: NULL, with rt_last_error() saying so. */
+const rt_scene_desc* rt_json_scene_desc_lit(const rt_json_scene* scene);
 
 /* The RayTracer's width/height after loading (changed by a camera "resolution" entry). */
 void rt_json_scene_size(const rt_json_scene* scene, int32_t* width, int32_t* height);
