@@ -492,8 +492,8 @@ RT_HD bool sphere_filter_pass(const SphereFilter& s, const FilterRay& r) {
     return !(__builtin_fmaf(hb, hb, -cc) < 0.0f);
 }
 
-// Scene features a trace kernel is compiled for (FEAT template arguments; the lean kernels, pt_trace.hip
-// scene_lean): planes, boxes and triangles among the primitives, every background (else the sky gradient
+// Scene features a trace kernel is compiled for (FEAT template arguments; the lean kernels, kernel_select.h
+// select_kernel): planes, boxes and triangles among the primitives, every background (else the sky gradient
 // only), the orthographic camera and the stochastic / centre AA modes (else the perspective camera with
 // supersampling).  A kernel compiled without a feature holds none of its code, nor the scene constants
 // that code reads, so fewer scalars stay live across the segment loop (SGPR spills).
@@ -1341,7 +1341,7 @@ template <int ACC> constexpr int walk_of() {
     return ACC == ACC_BRUTE_TEX || ACC == ACC_BRUTE_LIT ? ACC_BRUTE
          : ACC == ACC_BVH_STACK_TEX || ACC == ACC_BVH_STACK_LIT ? ACC_BVH_STACK : ACC;
 }
-// The lean kernels (pt_trace.hip scene_feat): compiled for the common scene shapes only, the sky
+// The lean kernels (kernel_select.h select_kernel): compiled for the common scene shapes only, the sky
 // gradient, the perspective camera and supersampling AA —
 //   ACC_GRID_LDS_LEAN: ACC_GRID_LDS for spheres alone (no planes, boxes or triangles; RTOW);
 //   ACC_BVH_STACK_LEAN: ACC_BVH_STACK without boxes (spheres, planes, triangles; config 5)

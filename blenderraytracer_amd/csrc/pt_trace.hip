@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pt_launch.h"
+#include "kernel_select.h"
 #include "pool_order.h"
 #include "queue_slots.h"
 
@@ -35,26 +36,6 @@ struct TraceArgs {
 };
 static_assert(offsetof(TraceArgs<double>, sc) == 0 && offsetof(TraceArgs<float>, sc) == 0, "sc first");
 
-// One wave (an 8x8 pixel tile) per workgroup: one-wave workgroups measured fastest (RTOW f64 4350 vs
-// 4190 Msamples/s for 16x16 tiles, mesh50k 3342 vs 3094): finer work items shorten the frame's tail.
-#ifndef RT_MIN_WAVES_PER_SIMD
-#define RT_MIN_WAVES_PER_SIMD 6   // brute force: 80 VGPRs.  At 8 waves (64 VGPRs) the binary64 pool kernel
-#endif                            // spills 300 B/lane: Cornell f64 5175 (8) / 6730 (4) / 6830 (6) Msamples/s,
-                                  // f32 9274 (8) / 9680 (4) / 9978 (6)
-#ifndef RT_BVH_WAVES_PER_SIMD
-#define RT_BVH_WAVES_PER_SIMD 4   // binary64 BVH walk: 128 VGPRs (measured 3/4/5 waves: 5405/5462/5092)
-#endif
-#ifndef RT_BVH_WAVES_F32
-#define RT_BVH_WAVES_F32 5        // binary32 BVH walk: 96 VGPRs (measured 4/5/6 waves: 6070/6628/6542)
-#endif
-
-#ifndef RT_SPHERES_WAVES_PER_SIMD
-#define RT_SPHERES_WAVES_PER_SIMD 5   // binary64 sphere-only walk (ACC_BVH_SPHERES): 96 VGPRs, 13 spilled to
-#endif                                // scratch in cold paths; RTOW 128 spp 4 / 5 waves: 7119 / 7335 Msamples/s
-#ifndef RT_SPHERES_WAVES_F32
-#define RT_SPHERES_WAVES_F32 6       // binary32 sphere-only walk: 80 VGPRs (5 / 6 waves: 8536 / 8800 RTOW f32)
-#endif
-
 // the binary64 stack is static (24 entries) unless RT_F64_DYN_STACK (A/B): then, as binary32's, dynamic
 // LDS sized to the scene's deepest leaf, which 6 waves/SIMD would need.  Measured on the sphere-only
 // kernel, RTOW 512 spp: static 5 waves 7962, dynamic 5 waves 7870, dynamic 6 waves (57 VGPRs spilled)
@@ -65,35 +46,11 @@ static_assert(offsetof(TraceArgs<double>, sc) == 0 && offsetof(TraceArgs<float>,
 template <class R, int ACC>
 constexpr bool dyn_stack() { return sizeof(R) == 4 || (RT_F64_DYN_STACK != 0 && ACC == ACC_BVH_SPHERES); }
 
-#ifndef RT_LDS_OCC_F64
-#define RT_LDS_OCC_F64 4          // waves/SIMD of the LDS-node kernel (trace_pool_lds_kernel)
-#endif
-#ifndef RT_LDS_OCC_F32
-#define RT_LDS_OCC_F32 6
-#endif
-
-#ifndef RT_GRID_WAVES_PER_SIMD
-#define RT_GRID_WAVES_PER_SIMD 5
-#endif
-#ifndef RT_GRID_WAVES_F32
-#define RT_GRID_WAVES_F32 6
-#endif
 // walks with a per-lane LDS stack (the ordered BVH walks)
 template <int ACC>
 constexpr bool uses_stack() {
     return walk_of<ACC>() == ACC_BVH_STACK || ACC == ACC_BVH_SPHERES || ACC == ACC_BVH_SPHERES_LDS || ACC == ACC_BVH_TRI_LDS ||
            ACC == ACC_BVH_STACK_LEAN;
-}
-
-template <class R, int ACC>
-constexpr int waves_per_simd() {
-    if constexpr (ACC == ACC_GRID || ACC == ACC_GRID_LDS || ACC == ACC_GRID_LDS_LEAN)
-        return sizeof(R) == 8 ? RT_GRID_WAVES_PER_SIMD : RT_GRID_WAVES_F32;
-    if constexpr (ACC == ACC_BVH_SPHERES) return sizeof(R) == 8 ? RT_SPHERES_WAVES_PER_SIMD : RT_SPHERES_WAVES_F32;
-    if constexpr (ACC == ACC_BVH_SPHERES_LDS) return sizeof(R) == 8 ? RT_LDS_OCC_F64 : RT_LDS_OCC_F32;
-    if constexpr (ACC == ACC_BVH_TRI_LDS) return sizeof(R) == 8 ? RT_BVH_WAVES_PER_SIMD : RT_BVH_WAVES_F32;
-    // (the textured kernels take their walks' occupancy: texture_value is out of line)
-    return walk_of<ACC>() >= ACC_BVH ? (sizeof(R) == 8 ? RT_BVH_WAVES_PER_SIMD : RT_BVH_WAVES_F32) : RT_MIN_WAVES_PER_SIMD;
 }
 
 // Per-wave reduction of the lanes' work counters into Counters::totals (one 64-bit atomic each).
@@ -596,37 +553,6 @@ __device__ __forceinline__ void pool_item(const TraceArgs<R>& args, double* __re
 // exactly as there, so the sums are bit-identical to it.  The queue is one of kPoolQueues counter
 // pairs {next item, waves exited}, held by one launch at a time (acquire_queue / hold_queue, queue_slots.h):
 // the last wave to exit sets both back to 0.
-// Waves per workgroup: a multiple of 4, so that every workgroup puts the same number of waves on
-// each SIMD (10-wave workgroups at 5 waves/SIMD left one SIMD a wave short of the second workgroup:
-// one workgroup per CU, RTOW -28 %)
-#ifndef RT_LDS_WAVES_F64
-#define RT_LDS_WAVES_F64 8        // 2 workgroups per CU at 4 waves/SIMD
-#endif
-#ifndef RT_LDS_WAVES_F32
-#define RT_LDS_WAVES_F32 12       // 2 workgroups per CU at 6 waves/SIMD
-#endif
-// the grid's LDS kernel (ACC_GRID_LDS) holds no stacks: smaller workgroups, each with its own copy
-#ifndef RT_GRID_LDS_WAVES_F64
-#define RT_GRID_LDS_WAVES_F64 4   // 5 workgroups per CU at 5 waves/SIMD
-#endif
-#ifndef RT_GRID_LDS_WAVES_F32
-#define RT_GRID_LDS_WAVES_F32 12  // 2 workgroups per CU at 6 waves/SIMD (8: 3 per CU, -0.7 %)
-#endif
-// the triangle tree's LDS kernel (ACC_BVH_TRI_LDS): one workgroup per CU at 4 waves/SIMD, so that the
-// CU's one copy of the top levels is as large as its LDS allows beside the 16 waves' stacks and partials
-// (binary32, 5 waves/SIMD: 4-wave workgroups, five copies per CU)
-#ifndef RT_TRI_LDS_WAVES_F64
-#define RT_TRI_LDS_WAVES_F64 16
-#endif
-#ifndef RT_TRI_LDS_WAVES_F32
-#define RT_TRI_LDS_WAVES_F32 4
-#endif
-template <class R, int ACC = ACC_BVH_SPHERES_LDS>
-constexpr int lds_waves() {
-    if constexpr (ACC == ACC_GRID_LDS || ACC == ACC_GRID_LDS_LEAN) return sizeof(R) == 8 ? RT_GRID_LDS_WAVES_F64 : RT_GRID_LDS_WAVES_F32;
-    if constexpr (ACC == ACC_BVH_TRI_LDS) return sizeof(R) == 8 ? RT_TRI_LDS_WAVES_F64 : RT_TRI_LDS_WAVES_F32;
-    return sizeof(R) == 8 ? RT_LDS_WAVES_F64 : RT_LDS_WAVES_F32;
-}
 constexpr int kPoolQueues = 1024;
 __device__ uint32_t g_pool_queue[2 * kPoolQueues];
 
@@ -651,8 +577,9 @@ void trace_pool_lds_kernel(const TraceArgs<R> args, double* __restrict__ part, c
                            const int items, const int qi) {
     constexpr int W = lds_waves<R, ACC>();
     const SceneView<R>& sc = args.sc;
-    // dynamic LDS: [child boxes 48 B x n][child references 8 B x n][W stacks of entries x 64 ints], or
-    // for the grid [records][cell offsets]
+    // dynamic LDS: [child boxes 48 B x n][child references 8 B x n][W stacks of entries x 64 ints] (WideLds,
+    // kernel_select.h; written out here: through a shared staging helper the node kernels' code came out
+    // different), or for the grid [records][cell offsets]
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
     __shared__ double acc_all[W * 3 * 64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -770,10 +697,7 @@ __global__ __launch_bounds__(64) void reduce_gate_kernel(const ReduceGate g) {
 }
 
 bool trace_uses_pool() {
-    static const bool v = [] {             // thread-safe initialization (renders on several threads)
-        const char* e = getenv("RT_SAMPLE_POOL");
-        return !(e && e[0] == '0');
-    }();
+    static const bool v = !(getenv("RT_SAMPLE_POOL") && getenv("RT_SAMPLE_POOL")[0] == '0');   // thread-safe initialization
     return v;
 }
 
@@ -787,10 +711,7 @@ bool trace_uses_pool() {
 // 6947; 4K x 128 c23 / c45 7331 / 7393; mesh50k 256 spp c12 / c16 / c24 / c32 6786 / 6673 / 6687 /
 // 6391; Cornell 512^2 x 64 spp (4096 tiles) 4.  RT_POOL_CHUNK overrides (A/B runs).
 static int pool_chunk(int ns, int tiles, bool tri_bvh) {
-    static const int v = [] {
-        const char* e = getenv("RT_POOL_CHUNK");
-        return e ? std::max(1, atoi(e)) : 0;
-    }();
+    static const int v = getenv("RT_POOL_CHUNK") ? std::max(1, env_int("RT_POOL_CHUNK", 1)) : 0;
     if (v) return v;
     int c = std::min(128, std::max(4, (int)((tri_bvh ? 0.75 : 2.0) * std::sqrt((double)ns) + 0.5)));
     const int cmax = tri_bvh ? c : std::min(128, std::max(4, (int)(4.0 * std::sqrt((double)ns) + 0.5)));
@@ -882,87 +803,6 @@ size_t pool_partial_bytes(int cw, int ch, int ns, bool tri_bvh, int chunk_overri
     const int tiles = crop_tiles(cw, ch), chunk = chunk_override > 0 ? chunk_override : pool_chunk(ns, tiles, tri_bvh);
     const size_t chunks = (size_t)((ns + chunk - 1) / chunk);
     return chunks > 1 ? chunks * tiles * kPartialBytesPerTile : 0;
-}
-
-// Which sphere-only launches read the nodes from LDS: binary32 (RTOW 256 spp, 6 waves/SIMD: 9752 vs
-// 9504 Msamples/s); binary64 only when asked (RT_LDS_NODES=2): RTOW's 481 nodes (27 KB) + 5 workgroups'
-// stacks and partials exceed 160 KiB at 5 waves/SIMD, and at 4 the LDS kernel (7497) is slower than the
-// one-wave kernel at 5 (7744; at 4: 7291).  RT_LDS_NODES=0: never (A/B).
-#ifndef RT_LDS_NODES
-#define RT_LDS_NODES 1
-#endif
-// Which grid launches read the grid from LDS (trace_pool_lds_kernel<.., ACC_GRID_LDS>): RT_LDS_GRID=0
-// never (A/B), 1 (default) whenever the copy fits
-#ifndef RT_LDS_GRID
-#define RT_LDS_GRID 1
-#endif
-// RT_MAT_LDS (A/B): the grid LDS kernel also stages the material records in LDS (the budget check then
-// counts them: fewer workgroups per CU when they do not fit beside the grid)
-#ifndef RT_MAT_LDS
-#define RT_MAT_LDS 0
-#endif
-template <class R>
-static size_t lds_grid_bytes(const SceneView<R>& sc) {
-    static const int v = [] {
-        const char* e = getenv("RT_LDS_GRID");
-        return e ? atoi(e) : RT_LDS_GRID;
-    }();
-    if (v < 1 || sc.num_grid_cells <= 0) return 0;
-    constexpr int W = lds_waves<R, ACC_GRID_LDS>();
-    const size_t b = ((grid_lds_bytes(sc) + 15) & ~(size_t)15) + (RT_MAT_LDS ? sizeof(MatRec<R>) * (size_t)sc.num_mats : 0);
-    // RT_MAT_LDS: one workgroup per CU fewer (4 instead of 5 binary64 grid workgroups)
-    const size_t budget = 160 * 1024 / (4 * waves_per_simd<R, ACC_GRID_LDS>() / W - (RT_MAT_LDS ? 1 : 0));
-    return b + (size_t)W * 3 * 64 * 8 + 256 <= budget ? b : 0;
-}
-
-// LDS of trace_pool_lds_kernel (dynamic part), 0 if not used for this scene or if its sphere tree does
-// not fit: the kernel's workgroups per CU share its 160 KiB
-template <class R>
-static size_t lds_nodes_bytes(const SceneView<R>& sc) {
-    static const int v = [] {
-        const char* e = getenv("RT_LDS_NODES");
-        return e ? atoi(e) : RT_LDS_NODES;
-    }();
-    if (v < (sizeof(R) == 8 ? 2 : 1) || sc.num_sphere_wide <= 0) return 0;
-    constexpr int W = lds_waves<R>();
-    const size_t b = (size_t)56 * sc.num_sphere_wide + (size_t)W * std::min(sc.stack_entries, RT_BVH_STACK) * 64 * 4;
-    const size_t budget = 160 * 1024 / (4 * waves_per_simd<R, ACC_BVH_SPHERES_LDS>() / W);
-    return b + (size_t)W * 3 * 64 * 8 + 256 <= budget ? b : 0;
-}
-
-// Which launches of scenes with a triangle tree run trace_pool_lds_kernel<.., ACC_BVH_TRI_LDS> (the top
-// levels of the triangle tree in LDS): RT_LDS_TRI = 0 (default) never, 1 binary64, 2 both precisions.
-// Measured (round 6, mesh50k 1080p x 128 spp f64, interleaved x2, identical images): the one-wave kernel
-// 6915 / 6845 Msamples/s; the persistent kernel with 1019 / 255 / 64 top nodes in LDS 6360-6369 /
-// 6319-6323 / 6238-6272, in 8-wave workgroups (507 nodes, two copies per CU) 6283-6336: the LDS nodes buy
-// +1.8 % over the same kernel without them, the persistent form loses 9 % against hardware-dispatched
-// one-wave workgroups (round 5's persistent one-wave kernel with per-XCD queues: -10 %) — DESIGN.md §4
-#ifndef RT_LDS_TRI
-#define RT_LDS_TRI 0
-#endif
-// the triangle-tree nodes a launch stages (0: the one-wave kernel): as many of the breadth-first prefix
-// (RT_TRI_TOP_NODES, or RT_TRI_LDS_NODES from the environment for A/B runs) as fit the CU's LDS beside
-// the workgroups' stacks and partials, at least 64
-template <class R>
-static int lds_tri_nodes(const SceneView<R>& sc) {
-    static const int v = [] {
-        const char* e = getenv("RT_LDS_TRI");
-        return e ? atoi(e) : RT_LDS_TRI;
-    }();
-    static const int cap = [] {
-        const char* e = getenv("RT_TRI_LDS_NODES");
-        return e ? std::max(0, std::min(atoi(e), RT_TRI_TOP_NODES)) : RT_TRI_TOP_NODES;
-    }();
-    if (v < (sizeof(R) == 8 ? 1 : 2) || sc.num_tri_wide <= 0) return 0;
-    constexpr int W = lds_waves<R, ACC_BVH_TRI_LDS>();
-    const long long budget = 160 * 1024 / (4 * waves_per_simd<R, ACC_BVH_TRI_LDS>() / W);
-    const long long fixed = (long long)W * std::min(sc.stack_entries, RT_BVH_STACK) * 64 * 4 + (long long)W * 3 * 64 * 8 + 256;
-    const long long n = std::min<long long>({(long long)sc.num_tri_wide, (long long)cap, (budget - fixed) / 56});
-    return n >= 64 ? (int)n : 0;
-}
-template <class R>
-static size_t lds_tri_bytes(const SceneView<R>& sc, int nodes) {
-    return (size_t)56 * nodes + (size_t)lds_waves<R, ACC_BVH_TRI_LDS>() * std::min(sc.stack_entries, RT_BVH_STACK) * 64 * 4;
 }
 
 // ---- ownership of the LDS pool launches' queues (queue_slots.h) ----
@@ -1221,56 +1061,32 @@ static hipError_t launch_lds_pool(const TraceArgs<R>& a, bool count, double* par
     return register_pool_launch(a.c, dev, qi, (uint32_t)items, stream);
 }
 
-// The lean kernels (feat_of, pt_core.h) serve launches whose scene has the sky gradient, the perspective
-// camera and supersampling AA, and the lean kernel's primitives: the grid's (ACC_GRID_LDS_LEAN) spheres
-// alone, the triangle BVH walk's (ACC_BVH_STACK_LEAN) and World order's (ACC_BRUTE_LEAN) no boxes (World
-// order: no triangles either).  RT_LEAN=0: never (A/B); 1 (default): all three; 2: the grid's only.
-// A scene with procedural textures (SceneView::num_tex) never takes them: launch_* route it to the F_TEX
-// kernels (ACC_BRUTE_TEX / ACC_BVH_STACK_TEX: one-wave pool and lane-per-pixel forms only) before the
-// walk is chosen, so scenes without textures launch exactly the kernels they launched before.
-#ifndef RT_LEAN
-#define RT_LEAN 1
-#endif
+// The one selection of every trace launch (kernel_select.h) with the process's knobs, read from the
+// environment once (thread-safe initialization: renders on several threads)
+static const SelectKnobs& process_knobs() {
+    static const SelectKnobs knobs = knobs_from_env();
+    return knobs;
+}
 template <class R>
-static bool scene_lean(const SceneView<R>& sc, const ImageParams& im, int feat) {
-    static const int v = [] {
-        const char* e = getenv("RT_LEAN");
-        return e ? atoi(e) : RT_LEAN;
-    }();
-    if (v == 0 || (v == 2 && feat != 0) || sc.num_tex > 0 || sc.num_lights > 0) return false;   // (no lean kernel evaluates textures or lights)
-    return (sc.num_planes == 0 || (feat & F_PLANES)) && (sc.num_boxes == 0 || (feat & F_BOXES)) &&
-           (sc.num_tri_nodes == 0 || (feat & F_TRIS)) && sc.background == 0 && !sc.cam_ortho && im.aa_mode == 0;
+static KernelChoice choose_kernel(const SceneView<R>& sc, int aa_mode, bool bvh, bool pool) {
+    return select_kernel<R>(scene_facts(sc), aa_mode, bvh, pool, process_knobs());
 }
 
-template <class R, int ACC>
-static hipError_t launch_pool_kernel(const TraceArgs<R>& a0, bool count, double* part, int tiles, int chunks,
-                                     int chunk, hipStream_t stream) {
-    if constexpr (ACC == ACC_BRUTE) {
-        if (scene_lean(a0.sc, a0.im, feat_of<ACC_BRUTE_LEAN>()))
-            return launch_onewave_pool<R, ACC_BRUTE_LEAN>(a0, count, part, tiles, chunks, chunk, stream);
-    } else if constexpr (ACC == ACC_GRID) {
-        if (const size_t lb = lds_grid_bytes(a0.sc)) {
-            if (scene_lean(a0.sc, a0.im, feat_of<ACC_GRID_LDS_LEAN>()))
-                return launch_lds_pool<R, ACC_GRID_LDS_LEAN>(a0, count, part, tiles, chunks, chunk, lb, stream);
-            return launch_lds_pool<R, ACC_GRID_LDS>(a0, count, part, tiles, chunks, chunk, lb, stream);
-        }
-    } else if constexpr (ACC == ACC_BVH_SPHERES) {
-        if (const size_t lb = lds_nodes_bytes(a0.sc))
-            return launch_lds_pool<R, ACC_BVH_SPHERES_LDS>(a0, count, part, tiles, chunks, chunk, lb, stream);
-    } else if constexpr (ACC == ACC_BVH_STACK) {
-        TraceArgs<R> a = a0;
-        a.sc.tri_lds_nodes = lds_tri_nodes(a.sc);
-        if (a.sc.tri_lds_nodes)
-            return launch_lds_pool<R, ACC_BVH_TRI_LDS>(a, count, part, tiles, chunks, chunk,
-                                                       lds_tri_bytes(a.sc, a.sc.tri_lds_nodes), stream);
-        if (scene_lean(a0.sc, a0.im, feat_of<ACC_BVH_STACK_LEAN>()))
-            return launch_onewave_pool<R, ACC_BVH_STACK_LEAN>(a0, count, part, tiles, chunks, chunk, stream);
-    }
-    return launch_onewave_pool<R, ACC>(a0, count, part, tiles, chunks, chunk, stream);
+// one pool launch of the chosen kernel
+template <class R>
+static hipError_t launch_pool_kernel(const KernelChoice& k, const TraceArgs<R>& a0, bool count, double* part, int tiles,
+                                     int chunks, int chunk, hipStream_t stream) {
+    TraceArgs<R> a = a0;
+    if (k.acc == ACC_BVH_TRI_LDS) a.sc.tri_lds_nodes = k.tri_lds_nodes;
+    return with_acc(k.acc, [&](auto tag) {
+        constexpr int ACC = decltype(tag)::value;
+        if constexpr (lds_form(ACC)) return launch_lds_pool<R, ACC>(a, count, part, tiles, chunks, chunk, k.lds_bytes, stream);
+        else return launch_onewave_pool<R, ACC>(a, count, part, tiles, chunks, chunk, stream);
+    });
 }
 
-template <class R, int ACC>
-static hipError_t launch_pool(const TraceArgs<R>& a0, bool count, hipStream_t stream) {
+template <class R>
+static hipError_t launch_pool(const KernelChoice& k, const TraceArgs<R>& a0, bool count, hipStream_t stream) {
     const ImageParams& im = a0.im;
     const int ns_all = im.s_end - im.s_begin;
     // the chunk choice depends on the scene, not on the walk, so BVH and brute force add the samples
@@ -1293,7 +1109,7 @@ static hipError_t launch_pool(const TraceArgs<R>& a0, bool count, hipStream_t st
         const int ns = a.im.s_end - b, chunks = (ns + chunk - 1) / chunk;
         if ((long long)tiles * chunks > 0x7FFFFFFFLL) return hipErrorInvalidConfiguration;
         double* part = chunks > 1 ? a0.c.part : nullptr;
-        if (const hipError_t e = launch_pool_kernel<R, ACC>(a, count, part, tiles, chunks, chunk, stream)) return e;
+        if (const hipError_t e = launch_pool_kernel(k, a, count, part, tiles, chunks, chunk, stream)) return e;
         if (part)
             hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)tiles), dim3(64), 0, stream, a.im, a.c.sum,
                                (const double*)part, tiles, chunks, (const uint32_t*)nullptr);
@@ -1303,51 +1119,24 @@ static hipError_t launch_pool(const TraceArgs<R>& a0, bool count, hipStream_t st
     return hipSuccess;
 }
 
-// RT_BVH_WALK=skip (A/B runs): the stackless preorder walk; default: the ordered two-child walk, in its
-// sphere-only form for scenes without triangles (RT_BVH_WALK=two: always the general form)
 template <class R>
-static int bvh_walk_mode(const SceneView<R>& sc) {
-    static const int v = [] {
-        const char* e = getenv("RT_BVH_WALK");
-        // A/B: skip = stackless walk, two = the general ordered walk, tree = the sphere tree even where
-        // the grid was chosen, grid = the grid wherever one was built
-        return e && !strncmp(e, "skip", 4) ? ACC_BVH : e && !strncmp(e, "two", 3) ? ACC_BVH_STACK
-             : e && !strncmp(e, "grid", 4) ? ACC_GRID : e && !strncmp(e, "tree", 4) ? -2 : ACC_BVH_SPHERES;
-    }();
-    if (sc.num_tri_nodes > 0) return v == ACC_BVH ? ACC_BVH : ACC_BVH_STACK;
-    const bool grid = sc.num_grid_cells > 0 && (v == ACC_GRID || (v == ACC_BVH_SPHERES && sc.use_grid));
-    return grid ? ACC_GRID : v == -2 || v == ACC_GRID ? ACC_BVH_SPHERES : v;
-}
-
-template <class R>
-bool trace_walks_grid(const SceneView<R>& sc) { return sc.num_tex == 0 && sc.num_lights == 0 && bvh_walk_mode(sc) == ACC_GRID; }
+bool trace_walks_grid(const SceneView<R>& sc) { return walk_report(choose_kernel(sc, 0, true, true).acc) == 2; }
 template bool trace_walks_grid<double>(const SceneView<double>&);
 template bool trace_walks_grid<float>(const SceneView<float>&);
-
-template <class R, int ACC>
-static hipError_t launch_acc(const TraceArgs<R>& a, bool count, bool pool, hipStream_t stream) {
-    if (pool) return launch_pool<R, ACC>(a, count, stream);
-    return launch_lane_kernel<R, ACC>(a, count, stream);
-}
 
 template <class R>
 hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Counters& c, bool bvh, bool pool,
                         hipStream_t stream) {
     if (im.cw <= 0 || im.ch <= 0 || im.s_end <= im.s_begin) return hipSuccess;
-    TraceArgs<R> a{sc, im, c};
+    const TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
-    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
-        return bvh ? launch_acc<R, ACC_BVH_STACK_LIT>(a, count, pool, stream)
-                   : launch_acc<R, ACC_BRUTE_LIT>(a, count, pool, stream);
-    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
-        return bvh ? launch_acc<R, ACC_BVH_STACK_TEX>(a, count, pool, stream)
-                   : launch_acc<R, ACC_BRUTE_TEX>(a, count, pool, stream);
-    if (!bvh) return launch_acc<R, ACC_BRUTE>(a, count, pool, stream);
-    const int mode = bvh_walk_mode(sc);
-    if (mode == ACC_BVH) return launch_acc<R, ACC_BVH>(a, count, pool, stream);
-    if (mode == ACC_BVH_SPHERES) return launch_acc<R, ACC_BVH_SPHERES>(a, count, pool, stream);
-    if (mode == ACC_GRID) return launch_acc<R, ACC_GRID>(a, count, pool, stream);
-    return launch_acc<R, ACC_BVH_STACK>(a, count, pool, stream);
+    const KernelChoice k = choose_kernel(sc, im.aa_mode, bvh, pool);
+    if (pool) return launch_pool(k, a, count, stream);
+    return with_acc(k.acc, [&](auto tag) {
+        constexpr int ACC = decltype(tag)::value;
+        if constexpr (lds_form(ACC)) return hipErrorInvalidValue;      // pool launches only: never chosen here
+        else return launch_lane_kernel<R, ACC>(a, count, stream);
+    });
 }
 
 template hipError_t launch_trace<double>(const SceneView<double>&, const ImageParams&, const Counters&, bool, bool, hipStream_t);
@@ -1365,11 +1154,13 @@ PoolPlan pool_plan(int cw, int ch, int ns, bool tri_bvh, int chunk) {
 
 // The pool kernel alone, every chunk (even a single one) into `part`: the sums are not touched, so
 // several such launches (batches) may run at once on different streams; launch_reduce adds them.
-template <class R, int ACC>
-static hipError_t launch_partials_acc(const TraceArgs<R>& a, bool count, const PoolPlan& p, double* part,
-                                      hipStream_t stream) {
+// launch_trace_partials, _batches and _bands prepare the image parameters and the plan; this launches.
+template <class R>
+static hipError_t launch_partials(const SceneView<R>& sc, const ImageParams& im, const Counters& c, bool bvh,
+                                  const PoolPlan& p, double* part, hipStream_t stream) {
     if ((long long)p.tiles * p.chunks > 0x7FFFFFFFLL) return hipErrorInvalidConfiguration;
-    return launch_pool_kernel<R, ACC>(a, count, part, p.tiles, p.chunks, p.chunk, stream);
+    return launch_pool_kernel(choose_kernel(sc, im.aa_mode, bvh, true), TraceArgs<R>{sc, im, c}, c.segs || c.draws, part,
+                              p.tiles, p.chunks, p.chunk, stream);
 }
 
 template <class R>
@@ -1378,20 +1169,7 @@ hipError_t launch_trace_partials(const SceneView<R>& sc, const ImageParams& im, 
     if (im.cw <= 0 || im.ch <= 0 || im.s_end <= im.s_begin) return hipSuccess;
     const PoolPlan p = pool_plan(im.cw, im.ch, im.s_end - im.s_begin, sc.num_tri_nodes > 0, im.pool_chunk);
     if (!part || part_bytes < p.part_bytes) return hipErrorInvalidValue;
-    TraceArgs<R> a{sc, im, c};
-    const bool count = c.segs || c.draws;
-    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
-        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_LIT>(a, count, p, part, stream)
-                   : launch_partials_acc<R, ACC_BRUTE_LIT>(a, count, p, part, stream);
-    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
-        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, p, part, stream)
-                   : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, p, part, stream);
-    if (!bvh) return launch_partials_acc<R, ACC_BRUTE>(a, count, p, part, stream);
-    const int mode = bvh_walk_mode(sc);
-    if (mode == ACC_BVH) return launch_partials_acc<R, ACC_BVH>(a, count, p, part, stream);
-    if (mode == ACC_BVH_SPHERES) return launch_partials_acc<R, ACC_BVH_SPHERES>(a, count, p, part, stream);
-    if (mode == ACC_GRID) return launch_partials_acc<R, ACC_GRID>(a, count, p, part, stream);
-    return launch_partials_acc<R, ACC_BVH_STACK>(a, count, p, part, stream);
+    return launch_partials(sc, im, c, bvh, p, part, stream);
 }
 
 template hipError_t launch_trace_partials<double>(const SceneView<double>&, const ImageParams&, const Counters&, bool,
@@ -1422,20 +1200,7 @@ hipError_t launch_trace_batches(const SceneView<R>& sc, const ImageParams& im0, 
     im.batch_samples = batch;
     im.batch_chunks = p.chunks;
     const PoolPlan all{p.tiles, p.chunk, p.chunks * nb, (size_t)nb * p.part_bytes};
-    TraceArgs<R> a{sc, im, c};
-    const bool count = c.segs || c.draws;
-    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
-        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_LIT>(a, count, all, part, stream)
-                   : launch_partials_acc<R, ACC_BRUTE_LIT>(a, count, all, part, stream);
-    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
-        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, all, part, stream)
-                   : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, all, part, stream);
-    if (!bvh) return launch_partials_acc<R, ACC_BRUTE>(a, count, all, part, stream);
-    const int mode = bvh_walk_mode(sc);
-    if (mode == ACC_BVH) return launch_partials_acc<R, ACC_BVH>(a, count, all, part, stream);
-    if (mode == ACC_BVH_SPHERES) return launch_partials_acc<R, ACC_BVH_SPHERES>(a, count, all, part, stream);
-    if (mode == ACC_GRID) return launch_partials_acc<R, ACC_GRID>(a, count, all, part, stream);
-    return launch_partials_acc<R, ACC_BVH_STACK>(a, count, all, part, stream);
+    return launch_partials(sc, im, c, bvh, all, part, stream);
 }
 
 template hipError_t launch_trace_batches<double>(const SceneView<double>&, const ImageParams&, const Counters&, bool, int,
@@ -1466,20 +1231,7 @@ hipError_t launch_trace_bands(const SceneView<R>& sc, const ImageParams& im0, co
     im.pool_chunk = p.chunk;
     im.bands = bands;
     im.band_chunks = p.chunks;
-    TraceArgs<R> a{sc, im, c};
-    const bool count = c.segs || c.draws;
-    if (sc.num_lights > 0)                     // direct lighting: the F_LIGHT kernels (textures included)
-        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_LIT>(a, count, p, part, stream)
-                   : launch_partials_acc<R, ACC_BRUTE_LIT>(a, count, p, part, stream);
-    if (sc.num_tex > 0)                        // textured scenes: the F_TEX kernels, whatever the walk choice
-        return bvh ? launch_partials_acc<R, ACC_BVH_STACK_TEX>(a, count, p, part, stream)
-                   : launch_partials_acc<R, ACC_BRUTE_TEX>(a, count, p, part, stream);
-    if (!bvh) return launch_partials_acc<R, ACC_BRUTE>(a, count, p, part, stream);
-    const int mode = bvh_walk_mode(sc);
-    if (mode == ACC_BVH) return launch_partials_acc<R, ACC_BVH>(a, count, p, part, stream);
-    if (mode == ACC_BVH_SPHERES) return launch_partials_acc<R, ACC_BVH_SPHERES>(a, count, p, part, stream);
-    if (mode == ACC_GRID) return launch_partials_acc<R, ACC_GRID>(a, count, p, part, stream);
-    return launch_partials_acc<R, ACC_BVH_STACK>(a, count, p, part, stream);
+    return launch_partials(sc, im, c, bvh, p, part, stream);
 }
 template hipError_t launch_trace_bands<double>(const SceneView<double>&, const ImageParams&, const Counters&, bool, int,
                                                double*, size_t, PoolPlan*, hipStream_t);
@@ -1497,12 +1249,42 @@ hipError_t launch_reduce(const ImageParams& im, double* sum, const double* part,
 }
 
 // ---- World.hit for given rays (rt_closest_hits: the BVH proof on device arithmetic) ----
+// One-wave workgroups.  An LDS mode's walk reads a copy staged as trace_pool_lds_kernel stages it (the
+// caller's barrier follows): the grid's [records][cell offsets], or the WideLds block of the sphere tree
+// or of the triangle tree's top levels with the wave's stacks
+template <class R, int ACC>
+__device__ __forceinline__ BvhStack stage_lds_wave(const SceneView<R>& sc, unsigned char* lds_dyn) {
+    BvhStack stk{nullptr, 0};
+    if constexpr (ACC == ACC_GRID_LDS || ACC == ACC_GRID_LDS_LEAN) {
+        rt_u4* grec = reinterpret_cast<rt_u4*>(lds_dyn);
+        int* gcell = reinterpret_cast<int*>(lds_dyn + grid_lds_rec_bytes(sc));
+        copy_grid_lds(sc, grec, gcell, threadIdx.x, 64);
+        stk.gcell = gcell;
+        stk.grec = grec;
+    } else {
+        constexpr bool TOP = ACC == ACC_BVH_TRI_LDS;
+        const WideLds l{TOP ? sc.tri_lds_nodes : sc.num_sphere_wide, min(sc.stack_entries, RT_BVH_STACK)};
+        rt_u4* box = reinterpret_cast<rt_u4*>(lds_dyn + l.boxes());
+        rt_u2* kid = reinterpret_cast<rt_u2*>(lds_dyn + l.kids());
+        copy_wide_lds(TOP ? sc.tri_wide : sc.sphere_wide, l.n, box, kid, threadIdx.x, 64);
+        stk = BvhStack{reinterpret_cast<int*>(lds_dyn + l.stacks()) + threadIdx.x, 64, box, kid};
+        if constexpr (TOP) stk.ntop = l.n;
+    }
+    return stk;
+}
 template <class R, int ACC>
 __global__ __launch_bounds__(64) void closest_hits_kernel(const SceneView<R> sc, const double* __restrict__ rays,
                                                           const size_t n, double* __restrict__ t_out,
                                                           int* __restrict__ kind_out, int* __restrict__ idx_out) {
-    __shared__ int stack[RT_BVH_STACK * 64];
-    const BvhStack stk{stack + threadIdx.x, 64};
+    BvhStack stk{nullptr, 0};
+    if constexpr (lds_form(ACC)) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
+        stk = stage_lds_wave<R, ACC>(sc, lds_dyn);
+        __syncthreads();
+    } else {
+        __shared__ int stack[RT_BVH_STACK * 64];
+        stk = BvhStack{stack + threadIdx.x, 64};
+    }
     const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
     if (r >= n) return;
     const double* q = rays + 6 * r;
@@ -1514,104 +1296,24 @@ __global__ __launch_bounds__(64) void closest_hits_kernel(const SceneView<R> sc,
     idx_out[r] = c.kind == HIT_NONE ? -1 : c.idx;
 }
 
-// ... through the LDS copy of the nodes (the walk of trace_pool_lds_kernel)
-template <class R>
-__global__ __launch_bounds__(64) void closest_hits_lds_kernel(const SceneView<R> sc, const double* __restrict__ rays,
-                                                              const size_t n, double* __restrict__ t_out,
-                                                              int* __restrict__ kind_out, int* __restrict__ idx_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];   // [boxes][references][stack]
-    const int nn = sc.num_sphere_wide;
-    rt_u4* box = reinterpret_cast<rt_u4*>(lds_dyn);
-    rt_u2* kid = reinterpret_cast<rt_u2*>(lds_dyn + 48 * nn);
-    copy_wide_lds(sc.sphere_wide, nn, box, kid, threadIdx.x, 64);
-    __syncthreads();
-    const BvhStack stk{reinterpret_cast<int*>(lds_dyn + 56 * nn) + threadIdx.x, 64, box, kid};
-    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (r >= n) return;
-    const double* q = rays + 6 * r;
-    const V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), d = mk<R>((R)q[3], (R)q[4], (R)q[5]);
-    Work w{0, 0, 0, 0, 0, 0};
-    const Closest<R> c = closest_hit_acc<R, ACC_BVH_SPHERES_LDS>(sc, o, d, w, stk);
-    t_out[r] = c.kind == HIT_NONE ? (double)INFINITY : (double)c.t;
-    kind_out[r] = c.kind;
-    idx_out[r] = c.kind == HIT_NONE ? -1 : c.idx;
-}
-
-// ... through the LDS copy of the grid (the walk of trace_pool_lds_kernel<.., ACC_GRID_LDS>)
-template <class R>
-__global__ __launch_bounds__(64) void closest_hits_grid_lds_kernel(const SceneView<R> sc, const double* __restrict__ rays,
-                                                                   const size_t n, double* __restrict__ t_out,
-                                                                   int* __restrict__ kind_out, int* __restrict__ idx_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];   // [records][cell offsets]
-    BvhStack stk{nullptr, 0};
-    rt_u4* grec = reinterpret_cast<rt_u4*>(lds_dyn);
-    int* gcell = reinterpret_cast<int*>(lds_dyn + grid_lds_rec_bytes(sc));
-    copy_grid_lds(sc, grec, gcell, threadIdx.x, 64);
-    __syncthreads();
-    stk.gcell = gcell;
-    stk.grec = grec;
-    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (r >= n) return;
-    const double* q = rays + 6 * r;
-    const V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), d = mk<R>((R)q[3], (R)q[4], (R)q[5]);
-    Work w{0, 0, 0, 0, 0, 0};
-    const Closest<R> c = closest_hit_acc<R, ACC_GRID_LDS>(sc, o, d, w, stk);
-    t_out[r] = c.kind == HIT_NONE ? (double)INFINITY : (double)c.t;
-    kind_out[r] = c.kind;
-    idx_out[r] = c.kind == HIT_NONE ? -1 : c.idx;
-}
-
-// ... through the LDS copy of the triangle tree's top levels (trace_pool_lds_kernel<.., ACC_BVH_TRI_LDS>'s
-// walk; sc.tri_lds_nodes set by the launch)
-template <class R>
-__global__ __launch_bounds__(64) void closest_hits_tri_lds_kernel(const SceneView<R> sc, const double* __restrict__ rays,
-                                                                  const size_t n, double* __restrict__ t_out,
-                                                                  int* __restrict__ kind_out, int* __restrict__ idx_out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];   // [boxes][references][stack]
-    const int nn = sc.tri_lds_nodes;
-    rt_u4* box = reinterpret_cast<rt_u4*>(lds_dyn);
-    rt_u2* kid = reinterpret_cast<rt_u2*>(lds_dyn + 48 * nn);
-    copy_wide_lds(sc.tri_wide, nn, box, kid, threadIdx.x, 64);
-    __syncthreads();
-    BvhStack stk{reinterpret_cast<int*>(lds_dyn + 56 * nn) + threadIdx.x, 64, box, kid};
-    stk.ntop = nn;
-    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
-    if (r >= n) return;
-    const double* q = rays + 6 * r;
-    const V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), d = mk<R>((R)q[3], (R)q[4], (R)q[5]);
-    Work w{0, 0, 0, 0, 0, 0};
-    const Closest<R> c = closest_hit_acc<R, ACC_BVH_TRI_LDS>(sc, o, d, w, stk);
-    t_out[r] = c.kind == HIT_NONE ? (double)INFINITY : (double)c.t;
-    kind_out[r] = c.kind;
-    idx_out[r] = c.kind == HIT_NONE ? -1 : c.idx;
-}
-
+// The walk of the kernel a pool launch of this scene runs (a lean kernel's: its general twin's, the same
+// walk with no primitive left out; a textured or lit kernel's: the plain two-child walk or World order)
 template <class R>
 hipError_t launch_closest_hits(const SceneView<R>& sc, bool bvh, const double* rays, size_t n, double* t, int* kind,
                                int* idx, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    const dim3 grid((unsigned)((n + 63) / 64));
-    if (bvh && (sc.num_tex > 0 || sc.num_lights > 0)) {                        // the walk the trace kernel runs
-        hipLaunchKernelGGL((closest_hits_kernel<R, ACC_BVH_STACK>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
-        return hipGetLastError();
-    }
-    const bool spheres = bvh && bvh_walk_mode(sc) == ACC_BVH_SPHERES;
-    if (bvh && bvh_walk_mode(sc) == ACC_BVH_STACK && lds_tri_nodes(sc)) {
-        SceneView<R> v = sc;
-        v.tri_lds_nodes = lds_tri_nodes(sc);
-        const size_t lb = (size_t)56 * v.tri_lds_nodes + (size_t)std::min(sc.stack_entries, RT_BVH_STACK) * 64 * 4;
-        hipLaunchKernelGGL((closest_hits_tri_lds_kernel<R>), grid, dim3(64), lb, stream, v, rays, n, t, kind, idx);
-    } else if (spheres && lds_nodes_bytes(sc)) {
-        const size_t lb = (size_t)56 * sc.num_sphere_wide + (size_t)std::min(sc.stack_entries, RT_BVH_STACK) * 64 * 4;
-        hipLaunchKernelGGL((closest_hits_lds_kernel<R>), grid, dim3(64), lb, stream, sc, rays, n, t, kind, idx);
-    } else if (spheres)
-        hipLaunchKernelGGL((closest_hits_kernel<R, ACC_BVH_SPHERES>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
-    else if (bvh && bvh_walk_mode(sc) == ACC_GRID && lds_grid_bytes(sc))
-        hipLaunchKernelGGL((closest_hits_grid_lds_kernel<R>), grid, dim3(64), lds_grid_bytes(sc), stream, sc, rays, n, t, kind, idx);
-    else if (bvh && bvh_walk_mode(sc) == ACC_GRID)
-        hipLaunchKernelGGL((closest_hits_kernel<R, ACC_GRID>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
-    else if (bvh) hipLaunchKernelGGL((closest_hits_kernel<R, ACC_BVH_STACK>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
-    else hipLaunchKernelGGL((closest_hits_kernel<R, ACC_BRUTE>), grid, dim3(64), 0, stream, sc, rays, n, t, kind, idx);
+    const KernelChoice k = choose_kernel(sc, 0, bvh, true);
+    SceneView<R> v = sc;
+    if (k.acc == ACC_BVH_TRI_LDS) v.tri_lds_nodes = k.tri_lds_nodes;
+    with_acc(k.acc, [&](auto tag) {
+        constexpr int ACC = walk_of<plain_of(decltype(tag)::value)>();
+        // one wave's share of the trace launch's dynamic LDS: the grid's copy, or the nodes and one stack
+        const size_t lb = !lds_form(ACC) ? 0 : ACC == ACC_GRID_LDS ? k.lds_bytes
+                        : WideLds{ACC == ACC_BVH_TRI_LDS ? v.tri_lds_nodes : v.num_sphere_wide,
+                                  std::min(v.stack_entries, RT_BVH_STACK)}.bytes(1);
+        hipLaunchKernelGGL((closest_hits_kernel<R, ACC>), dim3((unsigned)((n + 63) / 64)), dim3(64), lb, stream,
+                           v, rays, n, t, kind, idx);
+    });
     return hipGetLastError();
 }
 template hipError_t launch_closest_hits<double>(const SceneView<double>&, bool, const double*, size_t, double*, int*, int*,
@@ -1872,10 +1574,7 @@ hipError_t launch_gamma_thresholds(double gamma, GammaTable* T, hipStream_t stre
 hipError_t launch_finalize(const FinalizeParams& p, const double* sum, double* mean, float* post, uint8_t* rgba8,
                            hipStream_t stream, const GammaTable* thresholds) {
     if (p.n <= 0) return hipSuccess;
-    static const int cap = [] {               // A/B: at most this many preview workgroups (0: no cap)
-        const char* e = getenv("RT_PREVIEW_WGS");
-        return e ? std::max(0, atoi(e)) : 0;
-    }();
+    static const int cap = std::max(0, env_int("RT_PREVIEW_WGS", 0));   // A/B: at most this many preview workgroups (0: no cap)
     if (thresholds && !mean && !post && rgba8)
         hipLaunchKernelGGL(preview_kernel, dim3(cap ? std::min((p.n + 63) / 64, cap) : (p.n + 63) / 64), dim3(64), 0,
                            stream, p, sum, thresholds, rgba8);

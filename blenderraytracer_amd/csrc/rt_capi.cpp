@@ -524,12 +524,17 @@ int check_accel(const rt_scene* sc, const rt_settings* s) {
 // rt_settings.sum_order: the sample pool unless the caller asks for sample order (or RT_SAMPLE_POOL=0)
 bool use_pool(const rt_settings* s) { return s->sum_order == RT_SUM_POOL && trace_uses_pool(); }
 
+// f(the device scene's view in this precision)
+template <class F>
+auto with_view(const DeviceState& ds, int32_t precision, F&& f) {
+    return precision == RT_PREC_F32 ? f(ds.s32.view) : f(ds.s64.view);
+}
+
 hipError_t trace(const rt_scene* sc, const DeviceState& ds, const rt_settings* s, const ImageParams& im,
                  const Counters& c, hipStream_t st) {
     if (im.max_depth <= 0) return hipSuccess;   // rayColor(ray, depth<=0) is 0: nothing to trace
     const bool bvh = use_bvh(sc, s), pool = use_pool(s);
-    if (s->precision == RT_PREC_F32) return launch_trace<float>(ds.s32.view, im, c, bvh, pool, st);
-    return launch_trace<double>(ds.s64.view, im, c, bvh, pool, st);
+    return with_view(ds, s->precision, [&](const auto& v) { return launch_trace(v, im, c, bvh, pool, st); });
 }
 
 // One overlapped batch on one device: the pool kernel writes the batch's chunk partials into slot `j`
@@ -545,9 +550,9 @@ hipError_t trace_overlapped(const rt_scene* sc, DeviceState& ds, const rt_settin
     hipError_t e = hipSuccess;
     if (slot_used) e = hipStreamWaitEvent(ts, ds.reduced[j], 0);
     if (e == hipSuccess)
-        e = s->precision == RT_PREC_F32
-                ? launch_trace_partials<float>(ds.s32.view, im, c, bvh, part.p, part.n * sizeof(double), ts)
-                : launch_trace_partials<double>(ds.s64.view, im, c, bvh, part.p, part.n * sizeof(double), ts);
+        e = with_view(ds, s->precision, [&](const auto& v) {
+            return launch_trace_partials(v, im, c, bvh, part.p, part.n * sizeof(double), ts);
+        });
     if (e == hipSuccess) e = hipEventRecord(ds.traced[j], ts);
     if (e == hipSuccess) e = hipStreamWaitEvent(ds.stream, ds.traced[j], 0);
     if (e == hipSuccess) e = launch_reduce(im, c.sum, part.p, sc->tri_bvh, ds.stream, gate);
@@ -575,9 +580,9 @@ int trace_replica(rt_scene* sc, DeviceState& ds, MergeSlot& m, const rt_settings
     HIP_TRY(m.stage[j].ensure(bytes / sizeof(double)));
     if (!m.stage_free[j]) HIP_TRY(hipEventCreateWithFlags(&m.stage_free[j], hipEventDisableTiming));
     HIP_TRY(hipSetDevice(ds.device));
-    HIP_TRY(s->precision == RT_PREC_F32
-                ? launch_trace_partials<float>(ds.s32.view, im, c, bvh, part.p, part.n * sizeof(double), ts)
-                : launch_trace_partials<double>(ds.s64.view, im, c, bvh, part.p, part.n * sizeof(double), ts));
+    HIP_TRY(with_view(ds, s->precision, [&](const auto& v) {
+        return launch_trace_partials(v, im, c, bvh, part.p, part.n * sizeof(double), ts);
+    }));
     if (m.stage_used[j]) HIP_TRY(hipStreamWaitEvent(ts, m.stage_free[j], 0));
     HIP_TRY(hipMemcpyPeerAsync(m.stage[j].p, h.device, part.p, ds.device, bytes, ts));
     HIP_TRY(hipEventRecord(ds.traced[j], ts));              // trace + copy out done
@@ -759,7 +764,7 @@ void fill_stats(rt_stats* st, const rt_scene* sc, const rt_settings* s, const un
         st->prim_tests = totals[2] + totals[3] + totals[0] * brute;
         // a walk step reads a 64-B two-child node, or a grid cell's 8-B record range (node_visits then
         // counts cells)
-        const bool grid = s->precision == RT_PREC_F32 ? trace_walks_grid(sc->home.s32.view) : trace_walks_grid(sc->home.s64.view);
+        const bool grid = with_view(sc->home, s->precision, [](const auto& v) { return trace_walks_grid(v); });
         st->algorithmic_bytes = (grid ? 8.0 : 64.0) * totals[1] + 16.0 * totals[2] + 36.0 * totals[3] +
                                 24.0 * totals[0] * brute + 12.0 * (double)n;
     } else {
@@ -1280,9 +1285,9 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
                     fi.pool_chunk = fchunk;
                     fi.batch_ways = nsh;
                     const size_t fb = de.fused_part.n * sizeof(double);
-                    HIP_TRY(s->precision == RT_PREC_F32
-                                ? launch_trace_batches<float>(de.s32.view, fi, c, bvh, batch, de.fused_part.p, fb, de.tstream[0])
-                                : launch_trace_batches<double>(de.s64.view, fi, c, bvh, batch, de.fused_part.p, fb, de.tstream[0]));
+                    HIP_TRY(with_view(de, s->precision, [&](const auto& v) {
+                        return launch_trace_batches(v, fi, c, bvh, batch, de.fused_part.p, fb, de.tstream[0]);
+                    }));
                     HIP_TRY(hipEventRecord(de.fused_done, de.tstream[0]));
                 }
                 fused_launched = true;
@@ -1642,6 +1647,10 @@ int rt_trace_device_bands(rt_scene* sc, const rt_settings* s, double* d_sum, voi
         HIP_TRY(scratch_idle(ds));
         HIP_TRY(ds.part.ensure(plan.part_bytes / sizeof(double)));
     }
+    // the control words are reset from the host: the gates of the scratch's last user (the last bands of an
+    // earlier call that returned without a host synchronization) must have read theirs first, or such a gate
+    // finds its flag cleared, skips its band and leaves `stop` set for every band of this call
+    HIP_TRY(scratch_idle(ds));
     HIP_TRY(order_scratch(ds, st));
     for (int b = 0; b < nb; ++b) ctl_store(sc->ctl, kCtlFlag + b, 0);
     ctl_store(sc->ctl, kCtlStop, 0);
@@ -1659,9 +1668,9 @@ int rt_trace_device_bands(rt_scene* sc, const rt_settings* s, double* d_sum, voi
     const bool bvh = use_bvh(sc, s);
     PoolPlan used{};
     HIP_TRY(hipEventRecord(ds.ev[0], ts));
-    HIP_TRY(s->precision == RT_PREC_F32
-                ? launch_trace_bands<float>(ds.s32.view, im, c, bvh, nb, ds.part.p, ds.part.n * sizeof(double), &used, ts)
-                : launch_trace_bands<double>(ds.s64.view, im, c, bvh, nb, ds.part.p, ds.part.n * sizeof(double), &used, ts));
+    HIP_TRY(with_view(ds, s->precision, [&](const auto& v) {
+        return launch_trace_bands(v, im, c, bvh, nb, ds.part.p, ds.part.n * sizeof(double), &used, ts);
+    }));
     HIP_TRY(hipEventRecord(ds.ev[1], ts));
     HIP_TRY(hipEventRecord(ds.fused_done, ts));
     im.bands = nb;
@@ -1731,7 +1740,7 @@ int rt_scene_walk(rt_scene* sc, int32_t precision, int32_t accel) {
     const int rc = check_accel(sc, &s);
     if (rc) return rc;
     if (!use_bvh(sc, &s)) return 0;
-    const bool grid = precision == RT_PREC_F32 ? trace_walks_grid(sc->home.s32.view) : trace_walks_grid(sc->home.s64.view);
+    const bool grid = with_view(sc->home, precision, [](const auto& v) { return trace_walks_grid(v); });
     return grid ? 2 : 1;
 }
 
@@ -1757,8 +1766,9 @@ int rt_closest_hits(rt_scene* sc, int32_t precision, int32_t accel, const double
     if (e == hipSuccess) e = hipMemcpyAsync(d_rays.p, rays, 6 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
     const bool bvh = use_bvh(sc, &s);
     if (e == hipSuccess)
-        e = precision == RT_PREC_F32 ? launch_closest_hits<float>(ds.s32.view, bvh, d_rays.p, n, d_t.p, d_kind.p, d_idx.p, ds.stream)
-                                     : launch_closest_hits<double>(ds.s64.view, bvh, d_rays.p, n, d_t.p, d_kind.p, d_idx.p, ds.stream);
+        e = with_view(ds, precision, [&](const auto& v) {
+            return launch_closest_hits(v, bvh, d_rays.p, n, d_t.p, d_kind.p, d_idx.p, ds.stream);
+        });
     if (e == hipSuccess && t) e = hipMemcpyAsync(t, d_t.p, n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
     if (e == hipSuccess && kind) e = hipMemcpyAsync(kind, d_kind.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
     if (e == hipSuccess && index) e = hipMemcpyAsync(index, d_idx.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
@@ -1790,8 +1800,9 @@ int rt_occluded(rt_scene* sc, int32_t precision, int32_t accel, const double* ra
     if (e == hipSuccess) e = hipMemcpyAsync(d_tmax.p, tmax, n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
     const bool bvh = use_bvh(sc, &s);
     if (e == hipSuccess)
-        e = precision == RT_PREC_F32 ? launch_occluded<float>(ds.s32.view, bvh, d_rays.p, d_tmax.p, n, d_out.p, ds.stream)
-                                     : launch_occluded<double>(ds.s64.view, bvh, d_rays.p, d_tmax.p, n, d_out.p, ds.stream);
+        e = with_view(ds, precision, [&](const auto& v) {
+            return launch_occluded(v, bvh, d_rays.p, d_tmax.p, n, d_out.p, ds.stream);
+        });
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, n, hipMemcpyDeviceToHost, ds.stream);
     const hipError_t es = hipStreamSynchronize(ds.stream);
     if (e == hipSuccess) e = es;
@@ -1814,8 +1825,9 @@ int rt_texture_values(rt_scene* sc, int32_t precision, int32_t texture, const do
     if (e == hipSuccess) e = d_rgb.ensure(3 * n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pts.p, points, 3 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
     if (e == hipSuccess)
-        e = precision == RT_PREC_F32 ? launch_texture_values<float>(ds.s32.view, texture, d_pts.p, n, d_rgb.p, ds.stream)
-                                     : launch_texture_values<double>(ds.s64.view, texture, d_pts.p, n, d_rgb.p, ds.stream);
+        e = with_view(ds, precision, [&](const auto& v) {
+            return launch_texture_values(v, texture, d_pts.p, n, d_rgb.p, ds.stream);
+        });
     if (e == hipSuccess) e = hipMemcpyAsync(rgb, d_rgb.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
     const hipError_t es = hipStreamSynchronize(ds.stream);
     if (e == hipSuccess) e = es;

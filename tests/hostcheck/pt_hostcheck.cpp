@@ -7,6 +7,7 @@
 #include "../../blenderraytracer_amd/csrc/pt_path.h"
 #include "../../blenderraytracer_amd/csrc/scene_pack.h"
 #include "../../blenderraytracer_amd/csrc/pool_order.h"
+#include "../../blenderraytracer_amd/csrc/kernel_select.h"
 
 using namespace rt;
 
@@ -413,6 +414,42 @@ extern "C" long long ptc_band_order(int cw, int ch, int chunks, int bands, unsig
     }
     for (int b = 0; b < bands; ++b) counts[b] = band_items(im, b);
     return n;
+}
+
+// The kernel selection (kernel_select.h select_kernel, TEST TOOL) of the scene as rt_scene_create stages it.
+// knobs: {bvh_walk (ptc_parse_bvh_walk), lean, lds_grid, lds_nodes, lds_tri, tri_lds_nodes}, NULL = the defaults.
+// out[0..4] = the choice {acc, lds, lds_bytes, tri_lds_nodes, rt_scene_walk's answer}, out[5..18] = the
+// SceneFacts in declaration order, out[19..22] = {lds_waves, waves_per_simd} of the sphere-tree and the
+// triangle-tree LDS kernels in this precision (the budgets' inputs)
+template <class R>
+static int kernel_choice(const rt_scene_desc* d, int bvh, int pool, int aa_mode, const SelectKnobs& k, long long* out) {
+    HostView<R> hv;
+    if (!hv.init(d)) return -1;
+    const SceneFacts f = scene_facts(hv.v);
+    const KernelChoice c = select_kernel<R>(f, aa_mode, bvh != 0, pool != 0, k);
+    const long long v[] = {c.acc, c.lds, (long long)c.lds_bytes, c.tri_lds_nodes, walk_report(c.acc),
+                           f.num_lights, f.num_tex, f.num_tri_nodes, f.num_tri_wide, f.num_sphere_wide, f.num_grid_cells,
+                           f.use_grid, f.num_planes, f.num_boxes, f.background, f.cam_ortho, f.stack_entries, f.num_mats,
+                           (long long)f.grid_lds_bytes,
+                           lds_waves<R, ACC_BVH_SPHERES_LDS>(), waves_per_simd<R, ACC_BVH_SPHERES_LDS>(),
+                           lds_waves<R, ACC_BVH_TRI_LDS>(), waves_per_simd<R, ACC_BVH_TRI_LDS>()};
+    std::memcpy(out, v, sizeof(v));
+    return 0;
+}
+extern "C" int ptc_kernel_choice(const rt_scene_desc* d, int precision, int bvh, int pool, int aa_mode, const int* knobs,
+                                 long long* out) {
+    SelectKnobs k;
+    if (knobs) k = SelectKnobs{knobs[0], knobs[1], knobs[2], knobs[3], knobs[4], knobs[5]};
+    return precision == RT_PREC_F32 ? kernel_choice<float>(d, bvh, pool, aa_mode, k, out)
+                                    : kernel_choice<double>(d, bvh, pool, aa_mode, k, out);
+}
+// RT_BVH_WALK's value as SelectKnobs::bvh_walk holds it (NULL: unset)
+extern "C" int ptc_parse_bvh_walk(const char* value) { return parse_bvh_walk(value); }
+// the default knobs, in ptc_kernel_choice's order
+extern "C" void ptc_default_knobs(int* out) {
+    const SelectKnobs k;
+    const int v[] = {k.bvh_walk, k.lean, k.lds_grid, k.lds_nodes, k.lds_tri, k.tri_lds_nodes};
+    std::memcpy(out, v, sizeof(v));
 }
 
 // chunk_range (pool_order.h, TEST TOOL): (batch, chunk, first sample, end sample) of launch chunk gci

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck", "pt_hostcheck.cpp")
 DEPS = [SRC] + [os.path.join(ROOT, "blenderraytracer_amd", "csrc", f) for f in ("pt_core.h", "pt_path.h", "scene_pack.h",
-                                                                          "pool_order.h", "js_math.h")]
+                                                                          "pool_order.h", "kernel_select.h", "js_math.h")]
 LIB = os.path.join(HERE, "hostcheck", "_build", "libpt_hostcheck.so")
 _lib = None
 
@@ -143,3 +143,27 @@ def pool_order(cw, ch, chunks, one_wave=True):
     n = L.ptc_pool_order(cw, ch, chunks, int(one_wave), out.ctypes.data_as(C.POINTER(C.c_uint32)), par)
     assert n == tiles * chunks
     return out, par[0], par[1], par[2]
+
+
+KNOBS = ("bvh_walk", "lean", "lds_grid", "lds_nodes", "lds_tri", "tri_lds_nodes")
+FACTS = ("num_lights", "num_tex", "num_tri_nodes", "num_tri_wide", "num_sphere_wide", "num_grid_cells", "use_grid",
+         "num_planes", "num_boxes", "background", "cam_ortho", "stack_entries", "num_mats", "grid_lds_bytes")
+
+
+def kernel_choice(packed, precision, bvh, pool=True, aa_mode=0, **knobs):
+    """The trace kernel a launch of this scene runs (kernel_select.h select_kernel): a dict with the choice
+    (acc, lds, lds_bytes, tri_lds_nodes, walk = rt_scene_walk's answer), the scene's facts and the two node
+    kernels' occupancy constants.  knobs: the SelectKnobs fields by name; bvh_walk takes RT_BVH_WALK's string."""
+    L = lib()
+    L.ptc_kernel_choice.argtypes = [C.POINTER(capi.SceneDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                    C.POINTER(C.c_longlong)]
+    L.ptc_parse_bvh_walk.argtypes = [C.c_char_p]
+    k = (C.c_int * len(KNOBS))()
+    L.ptc_default_knobs(k)
+    for name, value in knobs.items():
+        k[KNOBS.index(name)] = L.ptc_parse_bvh_walk(value.encode()) if name == "bvh_walk" else value
+    out = (C.c_longlong * 23)()
+    assert L.ptc_kernel_choice(C.byref(packed.desc), precision, int(bvh), int(pool), aa_mode, k, out) == 0
+    res = dict(zip(("acc", "lds", "lds_bytes", "tri_lds_nodes", "walk") + FACTS, out[:19]))
+    res.update(zip(("sphere_lds_waves", "sphere_lds_occ", "tri_lds_waves", "tri_lds_occ"), out[19:]))
+    return res
