@@ -14,6 +14,9 @@ RT_DESC_TEXTURES = 0x54455834  # rt_scene_desc.extensions of a descriptor whose 
 RT_DESC_LIGHTS = 0x4C495434    # ... whose texture fields and light fields are filled
 RT_MAX_LIGHTS = 32
 RT_MAX_DEVICES = 8
+RT_GUIDED_MAX_LEVELS = 8
+RT_GUIDED_DEFAULT_LEVELS = 5
+RT_GUIDED_DEFAULT_SIGMAS = {"color": 1.0, "albedo": 0.1, "normal": 0.35, "depth": 0.05}   # RT_GUIDED_DEFAULT_SIGMA_*
 
 # enums (include/rt_hip.h)
 RT_OBJ_SPHERE, RT_OBJ_PLANE, RT_OBJ_BOX, RT_OBJ_TRIANGLE, RT_OBJ_MESH = range(5)
@@ -93,6 +96,16 @@ class Stats(C.Structure):
                 ("sphere_tests", C.c_uint64), ("tri_tests", C.c_uint64)]
 
 
+class GuidedParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("_pad", C.c_int32), ("sigma_color", C.c_double), ("sigma_albedo", C.c_double),
+                ("sigma_normal", C.c_double), ("sigma_depth", C.c_double)]
+
+
+class AovOutput(C.Structure):
+    _fields_ = [("albedo", C.POINTER(C.c_float)), ("normal", C.POINTER(C.c_float)), ("depth", C.POINTER(C.c_float)),
+                ("kind", C.POINTER(C.c_int32)), ("index", C.POINTER(C.c_int32))]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_double, C.c_void_p)
 BAND_FN = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_void_p)   # rt_band_fn
 
@@ -122,6 +135,11 @@ EXPORTS = {
     "rt_render_checkpoint": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_int32)]),
     "rt_render_resume": (C.c_int, [C.c_void_p, C.POINTER(Settings), C.POINTER(C.c_double), C.c_int32,
                                    C.POINTER(Output), PROGRESS_FN, C.c_void_p, C.POINTER(Stats)]),
+    "rt_aovs": (C.c_int, [C.c_void_p, C.POINTER(Settings), C.POINTER(AovOutput)]),
+    "rt_aovs_device": (C.c_int, [C.c_void_p, C.POINTER(Settings), C.c_void_p, C.c_void_p]),
+    "rt_guided_filter_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GuidedParams), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "rt_scene_set_guided": (C.c_int, [C.c_void_p, C.POINTER(GuidedParams)]),
     # include/rt_scene_json.h (host-only scene-JSON loader)
     "rt_json_scene_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_json_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),

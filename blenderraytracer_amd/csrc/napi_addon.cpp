@@ -457,6 +457,19 @@ napi_value render(napi_env env, napi_callback_info info) {
         return throw_err(env, "render: settings.devices must be an Array of at most 8 device ordinals");
     }
     st.device_count = nd;
+    // settings.guided: the edge-aware guided filter of the final epilogue (rt_scene_set_guided), set or cleared
+    // here, before the render is queued; the other guided* keys default to the header's
+    {
+        rt_guided_params gp{(int32_t)get_num(env, s, "guidedLevels", RT_GUIDED_DEFAULT_LEVELS), 0,
+                            get_num(env, s, "guidedSigmaColor", RT_GUIDED_DEFAULT_SIGMA_COLOR),
+                            get_num(env, s, "guidedSigmaAlbedo", RT_GUIDED_DEFAULT_SIGMA_ALBEDO),
+                            get_num(env, s, "guidedSigmaNormal", RT_GUIDED_DEFAULT_SIGMA_NORMAL),
+                            get_num(env, s, "guidedSigmaDepth", RT_GUIDED_DEFAULT_SIGMA_DEPTH)};
+        if (rt_scene_set_guided(box->sc, get_num(env, s, "guided", 0) != 0 ? &gp : nullptr) != RT_OK) {
+            delete job;
+            return throw_err(env, std::string("render: ") + rt_last_error());
+        }
+    }
     job->want_mean = get_num(env, s, "wantMean", 0) != 0;
     job->want_counts = get_num(env, s, "wantCounts", 0) != 0;
     job->want_post = get_num(env, s, "wantPost", 1) != 0;      // the post-gamma Float32 frame (default on)
@@ -524,6 +537,46 @@ napi_value render(napi_env env, napi_callback_info info) {
     NAPI_OK(napi_queue_async_work(env, job->work));
     box->busy = true;
     return promise;
+}
+
+// aovs(scene, settings) -> {albedo, normal: Float32Array(3 per pixel), depth: Float32Array, kind, index: Int32Array}:
+// the feature buffers of the primary hit (rt_aovs) for the settings' frame or crop; synchronous (one ray per pixel)
+napi_value aovs(napi_env env, napi_callback_info info) {
+    size_t argc = 2;
+    napi_value argv[2];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    SceneBox* box = argc >= 2 ? get_box(env, argv[0]) : nullptr;
+    if (!box || !box->sc) return throw_err(env, "aovs(scene, settings)");
+    if (box->busy) return throw_err(env, "aovs: a render is in flight");
+    napi_value s = argv[1];
+    rt_settings st{};
+    st.width = (int32_t)get_num(env, s, "width", 0);
+    st.height = (int32_t)get_num(env, s, "height", 0);
+    st.crop_x0 = (int32_t)get_num(env, s, "cropX0", 0);
+    st.crop_y0 = (int32_t)get_num(env, s, "cropY0", 0);
+    st.crop_w = (int32_t)get_num(env, s, "cropW", 0);
+    st.crop_h = (int32_t)get_num(env, s, "cropH", 0);
+    st.precision = (int32_t)get_num(env, s, "precision", RT_PREC_F64);
+    st.accel = (int32_t)get_num(env, s, "accel", RT_ACCEL_AUTO);
+    const int cw = st.crop_w > 0 ? st.crop_w : st.width, ch = st.crop_h > 0 ? st.crop_h : st.height;
+    if (cw <= 0 || ch <= 0) return throw_err(env, "aovs: width/height must be positive");
+    const size_t n = (size_t)cw * ch;
+    const struct { const char* key; napi_typedarray_type type; size_t count; } outs[5] = {
+        {"albedo", napi_float32_array, 3 * n}, {"normal", napi_float32_array, 3 * n}, {"depth", napi_float32_array, n},
+        {"kind", napi_int32_array, n}, {"index", napi_int32_array, n}};
+    void* ptr[5];
+    napi_value res;
+    NAPI_OK(napi_create_object(env, &res));
+    for (int k = 0; k < 5; ++k) {
+        napi_value ab, arr;
+        NAPI_OK(napi_create_arraybuffer(env, outs[k].count * 4, &ptr[k], &ab));
+        NAPI_OK(napi_create_typedarray(env, outs[k].type, outs[k].count, ab, 0, &arr));
+        NAPI_OK(napi_set_named_property(env, res, outs[k].key, arr));
+    }
+    const rt_aov_output ao{static_cast<float*>(ptr[0]), static_cast<float*>(ptr[1]), static_cast<float*>(ptr[2]),
+                           static_cast<int32_t*>(ptr[3]), static_cast<int32_t*>(ptr[4])};
+    if (rt_aovs(box->sc, &st, &ao) != RT_OK) return throw_err(env, std::string("aovs: ") + rt_last_error());
+    return res;
 }
 
 napi_value cancel(napi_env env, napi_callback_info info) {
@@ -610,6 +663,7 @@ napi_value init(napi_env env, napi_value exports) {
     const napi_property_descriptor props[] = {
         {"createScene", nullptr, create_scene, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"render", nullptr, render, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+        {"aovs", nullptr, aovs, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"cancel", nullptr, cancel, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"checkpoint", nullptr, checkpoint, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"checkpointSamples", nullptr, checkpoint_samples, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

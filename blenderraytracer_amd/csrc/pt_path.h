@@ -482,4 +482,80 @@ RT_HD PixelResult trace_pixel(const SceneView<R>& sc, const ImageParams& im, int
     }
 }
 
+// ---- feature buffers (AOVs) of the primary hit: the guides of the guided filter (pt_guided.h) ----
+// One ray through the centre of pixel (i, j) (j bottom-up; the RT_AA_CENTER formula) from a pinhole — camera_ray
+// with the lens offset exactly zero, so no random number is drawn: perspective o = cam_o, d = ((llc + hor u) +
+// ver v) - o, not normalized; orthographic as camera_ray normalizes it.  The closest hit is the trace kernels'
+// own query and record.  g[0..2] albedo: the Lambertian / Metal albedo (a textured material: texture_value at
+// the hit point; binary32: aov_texture_value's pinned sine), (1, 1, 1) for a Dielectric, min(emission, 1) per channel for an Emissive; g[3..5] the record's
+// normal (facing the ray); g[6] = t |d| in R; g[7] = 0.  A miss: zeros and depth +inf.  Everything is computed
+// in R and stored as binary32.
+struct AovHit { int kind, idx; };
+// Texture.value for the albedo buffer.  Binary64: texture_value itself (pt_core.h), the trace kernels' function.
+// Binary32: the same operations with one difference — texture_value<float> takes the platform's sinf (the
+// binary32 fast mode keeps the device's own, pt_core.h js_sin), which differs in the last bit between the
+// device's library and a host's C library; a feature buffer is an output, so here the sine is V8's binary64
+// Math.sin (js_math.h: plain binary64 arithmetic, the same bits everywhere) of the widened argument, rounded to
+// binary32.  The buffer is then the same bits on the GPU and in the CPU build, and within an ulp or two of
+// the value the binary32 trace kernels attenuate with.  (|argument| > 2^19 pi/2: jsm::sin falls back to the
+// platform's function, not bit-pinned; no scene here gets near it.)
+RT_HD float aov_sin(float x) { return (float)jsm::sin((double)x); }
+template <class R>
+__host__ __device__ RT_COLD V3<R> aov_texture_value(const TexView<R>* tv, int tex, V3<R> p) {
+    if constexpr (sizeof(R) == 8) return texture_value<R>(tv, tex, p);
+    else {
+        const TexRec<R> t = tv->recs[tex];
+        const R s = t.scale;
+        if (t.type == TEX_CHECKER) {                                                  // textures.js:32-35
+            const R sines = (aov_sin(s * p.x) * aov_sin(s * p.y)) * aov_sin(s * p.z);
+            return sines < (R)0 ? mk(t.odd[0], t.odd[1], t.odd[2]) : mk(t.even[0], t.even[1], t.even[2]);
+        }
+        if (t.type == TEX_NOISE) return texture_value<R>(tv, tex, p);                 // no sine
+        const int* perm = tv->perms + 512 * t.perm;
+        if (t.type == TEX_MARBLE) {                                                   // :60-64
+            const R n = turbulence<R>(perm, p * s, 7);
+            const R m = (R)0.5 * ((R)1 + aov_sin(s * p.z + (R)10 * n)), w = (R)1 - m;
+            return mk<R>((R)0.9 * m + (R)0.6 * w, (R)0.8 * m + (R)0.4 * w, (R)0.7 * m + (R)0.3 * w);
+        }
+        const R k = s * (R)20;                                                        // wood :75-80
+        const R grain = perlin<R>(perm, p.x * k, p.y * k, p.z * k);
+        const R rings = aov_sin(s * sqrt(p.x * p.x + p.z * p.z) + grain * (R)10);
+        const R m = (R)0.5 * ((R)1 + rings), w = (R)1 - m;
+        return mk<R>((R)0.8 * m + (R)0.4 * w, (R)0.5 * m + (R)0.2 * w, (R)0.2 * m + (R)0.1 * w);
+    }
+}
+template <class R, int ACC>
+RT_HD AovHit aov_pixel(const SceneView<R>& sc, int width, int height, int i, int j, BvhStack stk, float* g) {
+    const R u = ((R)i + (R)0.5) / (R)width, v = ((R)j + (R)0.5) / (R)height;
+    const V3<R> o = mk<R>(sc.cam_o[0], sc.cam_o[1], sc.cam_o[2]);
+    const V3<R> llc = mk<R>(sc.cam_llc[0], sc.cam_llc[1], sc.cam_llc[2]);
+    const V3<R> hor = mk<R>(sc.cam_h[0], sc.cam_h[1], sc.cam_h[2]), ver = mk<R>(sc.cam_v[0], sc.cam_v[1], sc.cam_v[2]);
+    V3<R> d = ((llc + hor * u) + ver * v) - o;
+    if (sc.cam_ortho) d = normalize(d + mk<R>(sc.cam_w[0], sc.cam_w[1], sc.cam_w[2]) * (R)-1);
+    Work w{0, 0, 0, 0, 0, 0};
+    const Closest<R> c = closest_hit_acc<R, ACC>(sc, o, d, w, stk);
+    for (int k = 0; k < 8; ++k) g[k] = 0.0f;
+    if (c.kind == HIT_NONE) {
+        g[6] = INFINITY;
+        return AovHit{HIT_NONE, -1};
+    }
+    const Hit<R> h = hit_record<R>(sc, o, d, c);
+    const MatRec<R> m = sc.mats[h.mat];
+    V3<R> alb = mk<R>(1, 1, 1);                                               // Dielectric
+    if (m.type <= 1) {
+        alb = mk(m.c[0], m.c[1], m.c[2]);
+        if (sc.num_tex > 0) {
+            const TexView<R>* tv = tex_view(sc);
+            const int tex = tv->mat_tex[h.mat];
+            if (tex >= 0) alb = aov_texture_value<R>(tv, tex, h.p);
+        }
+    } else if (m.type == 3) {
+        alb = mk(m.c[0] > (R)1 ? (R)1 : m.c[0], m.c[1] > (R)1 ? (R)1 : m.c[1], m.c[2] > (R)1 ? (R)1 : m.c[2]);
+    }
+    g[0] = (float)alb.x; g[1] = (float)alb.y; g[2] = (float)alb.z;
+    g[3] = (float)h.n.x; g[4] = (float)h.n.y; g[5] = (float)h.n.z;
+    g[6] = (float)(c.t * sqrt(dot(d, d)));
+    return AovHit{c.kind, c.idx};
+}
+
 }  // namespace rt

@@ -20,6 +20,7 @@
 
 #include "../../include/rt_hip.h"
 #include "pt_launch.h"
+#include "pt_guided.h"
 #include "pool_order.h"
 #include "scene_pack.h"
 
@@ -393,6 +394,16 @@ struct rt_scene {
     uint32_t render_gen = 0;        // generation of the current render (device cancel words)
     uint32_t* ctl = nullptr;        // the render's control words (kCtl*), host address
     uint32_t* ctl_dev = nullptr;    // ... their device address (portable mapping: valid on every device)
+    // the guided filter (rt_scene_set_guided): while on, epilogue() filters the mean along the frame's feature
+    // buffers.  g_mean: sum / samples; guides: aov_kernel's records; g_ping / g_pong: the levels' frames
+    // (rt_guided_filter_device uses g_ping beside the caller's d_out).  g_used is recorded after every use of
+    // these buffers and waited for before the next, on whichever streams
+    bool guided_on = false;
+    rt_guided_params guided{};
+    DevBuf<double> g_mean, g_ping, g_pong;
+    DevBuf<float> guides;
+    hipEvent_t g_used = nullptr;
+    bool g_used_recorded = false;
     size_t ckpt_pixels = 0;         // progressive state of the last rt_render / rt_render_resume:
     int ckpt_done = 0;              // `home.sum` holds samples [sample_begin, ckpt_done) of ckpt_pixels pixels
     CkptKey ckpt_key{};             // ... of this frame, crop, first sample, precision and seed
@@ -474,22 +485,110 @@ hipError_t gamma_used(GammaSlot* g, hipStream_t st) {
     return e;
 }
 
+// RT_ACCEL_AUTO: the BVH unless the scene has almost no spheres/triangles (measured faster from 10
+// primitives (Cornell) to 50k (mesh50k), DESIGN.md "BVH")
+constexpr int kAutoBvhPrims = 8;
+
+bool use_bvh(const rt_scene* sc, const rt_settings* s) {
+    if (!sc->bvh_ok) return false;
+    return s->accel == RT_ACCEL_BVH || (s->accel == RT_ACCEL_AUTO && sc->bvh_prims >= kAutoBvhPrims);
+}
+
+// f(the device scene's view in this precision)
+template <class F>
+auto with_view(const DeviceState& ds, int32_t precision, F&& f) {
+    return precision == RT_PREC_F32 ? f(ds.s32.view) : f(ds.s64.view);
+}
+
+// the scene's guided-filter buffers on `st`: after their last use (on any stream), and marked used again
+hipError_t guided_scratch_begin(rt_scene* sc, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (!sc->g_used) e = hipEventCreateWithFlags(&sc->g_used, hipEventDisableTiming);
+    if (e == hipSuccess && sc->g_used_recorded) e = hipStreamWaitEvent(st, sc->g_used, 0);
+    return e;
+}
+hipError_t guided_scratch_end(rt_scene* sc, hipStream_t st) {
+    const hipError_t e = hipEventRecord(sc->g_used, st);
+    if (e == hipSuccess) sc->g_used_recorded = true;
+    return e;
+}
+// (a buffer that must grow is freed only once its last reader has finished)
+template <class T>
+hipError_t guided_ensure(rt_scene* sc, DevBuf<T>& b, size_t count) {
+    if (count <= b.n && b.p) return hipSuccess;
+    if (sc->g_used_recorded)
+        if (const hipError_t e = hipEventSynchronize(sc->g_used)) return e;
+    return b.ensure(count);
+}
+
+// The feature buffers of the settings' crop window into `guides` (8 floats per pixel) on `st`
+hipError_t aovs_on(const rt_scene* sc, const rt_settings* s, int cw, int ch, float* guides, int* kind, int* idx,
+                   hipStream_t st) {
+    const AovFrame f{s->width, s->height, s->crop_x0, s->crop_y0, cw, ch};
+    const bool bvh = use_bvh(sc, s);
+    return with_view(sc->home, s->precision, [&](const auto& v) { return launch_aovs(v, bvh, f, guides, kind, idx, st); });
+}
+
+// The levels of the filter: color -> ... -> out, level l into `out` when an even number of levels follow it,
+// else into `tmp`, so that no level runs in place (color, out and tmp are distinct frames)
+hipError_t guided_levels(int w, int h, const rt_guided_params& p, const double* color, const float* guides, double* out,
+                         double* tmp, hipStream_t st) {
+    const double* src = color;
+    for (int l = 0; l < p.levels; ++l) {
+        double* dst = (p.levels - 1 - l) % 2 == 0 ? out : tmp;
+        if (const hipError_t e = launch_guided_level(guided_level(w, h, p, l), src, guides, dst, st)) return e;
+        src = dst;
+    }
+    return hipSuccess;
+}
+
 // mean, toneMap, gammaCorrect (+ PostProcessor.denoise), RGBA8 on `st` (ray-tracer.js:208-276).
 // thresholds: an RGBA8-only epilogue through the gamma table (preview_kernel: the same bytes, 29 VGPRs
 // instead of finalize_kernel's 80)
+// While the guided filter is set (rt_scene_set_guided; full frames only, check_guided): the mean sum / samples,
+// the frame's feature buffers, the filter, then the same kernels on the filtered mean with samples = 1 (x / 1
+// is x: `mean` is the filtered mean).  `sum` is only read.
 hipError_t epilogue(rt_scene* sc, const rt_settings* s, int cw, int ch, const double* sum, double* mean, float* post,
                     uint8_t* rgba, hipStream_t st, bool thresholds = false) {
     FinalizeParams fp{cw * ch, s->samples, s->tone_map, s->exposure, s->gamma};
+    bool guided = false;
+    if (sc->guided_on) {
+        const size_t n = (size_t)cw * ch;
+        hipError_t e = guided_ensure(sc, sc->g_mean, 3 * n);
+        if (e == hipSuccess) e = guided_ensure(sc, sc->g_ping, 3 * n);
+        if (e == hipSuccess) e = guided_ensure(sc, sc->g_pong, 3 * n);
+        if (e == hipSuccess) e = guided_ensure(sc, sc->guides, 8 * n);
+        if (e == hipSuccess) e = guided_scratch_begin(sc, st);
+        if (e == hipSuccess) e = launch_mean(sum, s->samples, sc->g_mean.p, 3 * n, st);
+        if (e == hipSuccess) e = aovs_on(sc, s, cw, ch, sc->guides.p, nullptr, nullptr, st);
+        if (e == hipSuccess) e = guided_levels(cw, ch, sc->guided, sc->g_mean.p, sc->guides.p, sc->g_pong.p, sc->g_ping.p, st);
+        if (e != hipSuccess) return e;
+        sum = sc->g_pong.p;
+        fp.samples = 1;
+        thresholds = false;
+        guided = true;
+    }
+    hipError_t e = hipSuccess;
     if (thresholds && !s->denoise && !mean && !post && rgba)
         if (GammaSlot* g = gamma_table(sc, s->gamma)) {
-            const hipError_t e = launch_finalize(fp, sum, nullptr, nullptr, rgba, st, g->table());
+            e = launch_finalize(fp, sum, nullptr, nullptr, rgba, st, g->table());
             return e == hipSuccess ? gamma_used(g, st) : e;
         }
-    if (!s->denoise) return launch_finalize(fp, sum, mean, post, rgba, st);
-    hipError_t e = sc->post_raw.ensure(4 * (size_t)cw * ch);
-    if (e == hipSuccess) e = launch_finalize(fp, sum, mean, sc->post_raw.p, nullptr, st);
-    if (e == hipSuccess) e = launch_denoise(cw, ch, s->denoise_weights[0], s->denoise_weights[1], sc->post_raw.p, post, rgba, st);
+    if (!s->denoise) e = launch_finalize(fp, sum, mean, post, rgba, st);
+    else {
+        e = sc->post_raw.ensure(4 * (size_t)cw * ch);
+        if (e == hipSuccess) e = launch_finalize(fp, sum, mean, sc->post_raw.p, nullptr, st);
+        if (e == hipSuccess) e = launch_denoise(cw, ch, s->denoise_weights[0], s->denoise_weights[1], sc->post_raw.p, post, rgba, st);
+    }
+    if (e == hipSuccess && guided) e = guided_scratch_end(sc, st);
     return e;
+}
+
+// the guided filter reads every pixel's 5 x 5 x 2^l neighbourhood: the full frame, as `denoise`
+int check_guided(const rt_scene* sc, const rt_settings* s, int cw, int ch) {
+    if (sc->guided_on && (cw != s->width || ch != s->height))
+        return fail(RT_ERR_INVALID, "the guided filter needs the full frame (its taps reach across the image)");
+    return RT_OK;
 }
 
 ImageParams image_params(const rt_settings* s, int cw, int ch) {
@@ -505,15 +604,6 @@ ImageParams image_params(const rt_settings* s, int cw, int ch) {
     return im;
 }
 
-// RT_ACCEL_AUTO: the BVH unless the scene has almost no spheres/triangles (measured faster from 10
-// primitives (Cornell) to 50k (mesh50k), DESIGN.md "BVH")
-constexpr int kAutoBvhPrims = 8;
-
-bool use_bvh(const rt_scene* sc, const rt_settings* s) {
-    if (!sc->bvh_ok) return false;
-    return s->accel == RT_ACCEL_BVH || (s->accel == RT_ACCEL_AUTO && sc->bvh_prims >= kAutoBvhPrims);
-}
-
 int check_accel(const rt_scene* sc, const rt_settings* s) {
     if (s->accel == RT_ACCEL_BVH && !sc->bvh_ok)
         return fail(RT_ERR_INVALID, "BVH deeper than the %d-entry traversal stack (too many primitives): use "
@@ -523,12 +613,6 @@ int check_accel(const rt_scene* sc, const rt_settings* s) {
 
 // rt_settings.sum_order: the sample pool unless the caller asks for sample order (or RT_SAMPLE_POOL=0)
 bool use_pool(const rt_settings* s) { return s->sum_order == RT_SUM_POOL && trace_uses_pool(); }
-
-// f(the device scene's view in this precision)
-template <class F>
-auto with_view(const DeviceState& ds, int32_t precision, F&& f) {
-    return precision == RT_PREC_F32 ? f(ds.s32.view) : f(ds.s64.view);
-}
 
 hipError_t trace(const rt_scene* sc, const DeviceState& ds, const rt_settings* s, const ImageParams& im,
                  const Counters& c, hipStream_t st) {
@@ -901,6 +985,8 @@ void rt_scene_destroy(rt_scene* sc) {
     sc->home.release();
     (void)hipSetDevice(sc->home.device);
     sc->mean.release(); sc->post.release(); sc->post_raw.release();
+    sc->g_mean.release(); sc->g_ping.release(); sc->g_pong.release(); sc->guides.release();
+    if (sc->g_used) (void)hipEventDestroy(sc->g_used);
     for (MergeSlot& m : sc->merge) m.release();
     sc->rgba.release();
     for (GammaSlot& g : sc->gamma_slots) g.release();
@@ -1015,6 +1101,7 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
     if (!rc && s_local.batch_samples < 0) s_local.batch_samples = progress_batch(sc, s_in, cw, ch, -s_local.batch_samples);
     const rt_settings* s = &s_local;
     if (!rc) rc = check_accel(sc, s);
+    if (!rc) rc = check_guided(sc, s, cw, ch);
     if (rc) return rc;
     std::vector<DeviceState*> states;
     if ((rc = shard_states(sc, s, states))) return rc;
@@ -1842,9 +1929,85 @@ int rt_finalize_device(rt_scene* sc, const rt_settings* s, const double* d_sum, 
     if (!sc || !d_sum) return fail(RT_ERR_INVALID, "NULL argument");
     int cw, ch;
     int rc = check_settings(s, &cw, &ch);
+    if (!rc) rc = check_guided(sc, s, cw, ch);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(sc->home.device));
     HIP_TRY(epilogue(sc, s, cw, ch, d_sum, d_mean, d_post, d_rgba8, (hipStream_t)hip_stream, true));
+    return RT_OK;
+}
+
+int rt_scene_set_guided(rt_scene* sc, const rt_guided_params* p) {
+    // the parameters first: a bad set is RT_ERR_INVALID with or without a device (or a scene)
+    if (p && (p->levels < 1 || p->levels > RT_GUIDED_MAX_LEVELS))
+        return fail(RT_ERR_INVALID, "guided levels %d (1 .. %d)", p->levels, RT_GUIDED_MAX_LEVELS);
+    if (p && !guided_params_ok(p))
+        return fail(RT_ERR_INVALID, "guided sigmas (%g, %g, %g, %g): each must be > 0", p->sigma_color, p->sigma_albedo,
+                    p->sigma_normal, p->sigma_depth);
+    if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
+    sc->guided_on = p != nullptr;
+    if (p) sc->guided = *p;
+    return RT_OK;
+}
+
+int rt_aovs_device(rt_scene* sc, const rt_settings* s, float* d_guides, void* hip_stream) {
+    if (!sc || !d_guides) return fail(RT_ERR_INVALID, "NULL argument");
+    if (((uintptr_t)d_guides & 15) != 0) return fail(RT_ERR_INVALID, "d_guides is not 16-byte aligned");
+    int cw, ch;
+    int rc = check_settings(s, &cw, &ch);
+    if (!rc) rc = check_accel(sc, s);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(sc->home.device));
+    HIP_TRY(aovs_on(sc, s, cw, ch, d_guides, nullptr, nullptr, (hipStream_t)hip_stream));
+    return RT_OK;
+}
+
+int rt_aovs(rt_scene* sc, const rt_settings* s, const rt_aov_output* out) {
+    if (!sc || !out) return fail(RT_ERR_INVALID, "NULL argument");
+    int cw, ch;
+    int rc = check_settings(s, &cw, &ch);
+    if (!rc) rc = check_accel(sc, s);
+    if (rc) return rc;
+    const size_t n = (size_t)cw * ch;
+    DeviceState& ds = sc->home;
+    HIP_TRY(hipSetDevice(ds.device));
+    DevBuf<float> d_g;
+    DevBuf<int> d_kind, d_idx;
+    std::vector<float> g(8 * n);
+    hipError_t e = d_g.ensure(8 * n);
+    if (e == hipSuccess) e = d_kind.ensure(n);
+    if (e == hipSuccess) e = d_idx.ensure(n);
+    if (e == hipSuccess) e = aovs_on(sc, s, cw, ch, d_g.p, d_kind.p, d_idx.p, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g.data(), d_g.p, 8 * n * sizeof(float), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && out->kind) e = hipMemcpyAsync(out->kind, d_kind.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && out->index) e = hipMemcpyAsync(out->index, d_idx.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_g.release(); d_kind.release(); d_idx.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_aovs: %s", hipGetErrorString(e));
+    for (size_t q = 0; q < n; ++q) {                 // the guide records into the planar host arrays
+        const float* r = &g[8 * q];
+        if (out->albedo) { out->albedo[3 * q] = r[0]; out->albedo[3 * q + 1] = r[1]; out->albedo[3 * q + 2] = r[2]; }
+        if (out->normal) { out->normal[3 * q] = r[3]; out->normal[3 * q + 1] = r[4]; out->normal[3 * q + 2] = r[5]; }
+        if (out->depth) out->depth[q] = r[6];
+    }
+    return RT_OK;
+}
+
+int rt_guided_filter_device(rt_scene* sc, int32_t width, int32_t height, const rt_guided_params* p, const double* d_color,
+                            const float* d_guides, double* d_out, void* hip_stream) {
+    if (p && !guided_params_ok(p))
+        return fail(RT_ERR_INVALID, "guided parameters: levels %d (1 .. %d), sigmas (%g, %g, %g, %g) each > 0", p->levels,
+                    RT_GUIDED_MAX_LEVELS, p->sigma_color, p->sigma_albedo, p->sigma_normal, p->sigma_depth);
+    if (!sc || !p || !d_color || !d_guides || !d_out) return fail(RT_ERR_INVALID, "NULL argument");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID, "image %dx%d", width, height);
+    if (((uintptr_t)d_guides & 15) != 0) return fail(RT_ERR_INVALID, "d_guides is not 16-byte aligned");
+    if (d_out == d_color) return fail(RT_ERR_INVALID, "d_out must not be d_color (the filter never runs in place)");
+    const hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(sc->home.device));
+    if (p->levels > 1) HIP_TRY(guided_ensure(sc, sc->g_ping, 3 * (size_t)width * height));
+    HIP_TRY(guided_scratch_begin(sc, st));
+    HIP_TRY(guided_levels(width, height, *p, d_color, d_guides, d_out, sc->g_ping.p, st));
+    HIP_TRY(guided_scratch_end(sc, st));
     return RT_OK;
 }
 

@@ -5,7 +5,12 @@
 //                 [--exposure E] [--gamma G] [--denoise STRENGTH] [--precision f64|f32]
 //                 [--accel auto|bvh|brute] [--frames K] [--warmup W] [--batch B] [--device N]
 //                 [--out image.ppm|image.pam] [--lights]
+//                 [--guided] [--guided-levels N] [--guided-sigma C,A,N,Z] [--aovs PREFIX]
 //
+// --guided: the edge-aware guided filter over the linear mean (rt_scene_set_guided; --guided-levels and
+// --guided-sigma colour,albedo,normal,depth override the defaults and imply it)
+// --aovs PREFIX: the feature buffers of the primary hit (rt_aovs) as PREFIX.albedo.pfm, PREFIX.normal.pfm (colour
+// PFM) and PREFIX.depth.pfm (greyscale PFM), little-endian binary32, rows bottom-up as PFM has them
 // --lights: direct lighting from the scene's "lights" (rt_json_scene_desc_lit; off by default)
 //
 // Does what a reference user does in the browser: RayTracer(width, height) -> loadFromJSON(scene)
@@ -54,24 +59,37 @@ double now_ms() {
 // `value || dflt` for a numeric setting (updateRenderSettings, ray-tracer.js:556-565)
 double js_or(double v, double dflt) { return (v == 0 || v != v) ? dflt : v; }
 
+// a Portable Float Map: "PF" (3 channels) or "Pf" (1), a negative scale = little-endian, rows bottom to top
+void write_pfm(const std::string& path, const float* data, int width, int height, int channels) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) die("cannot write ", path.c_str());
+    fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", width, height);
+    for (int row = height - 1; row >= 0; --row) fwrite(data + (size_t)row * width * channels, sizeof(float), (size_t)width * channels, f);
+    fclose(f);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc < 2 || !strcmp(argv[1], "--help")) {
         fprintf(stderr, "usage: rt_render_cli scene.json [--width W --height H --spp S --depth D --seed N --aa MODE "
                         "--tone MAP --exposure E --gamma G --denoise STRENGTH --precision f64|f32 --accel auto|bvh|brute "
-                        "--frames K --warmup W --batch B --device N --out FILE --lights]\n");
+                        "--frames K --warmup W --batch B --device N --out FILE --lights --guided --guided-levels N "
+                        "--guided-sigma C,A,N,Z --aovs PREFIX]\n");
         return argc < 2 ? 2 : 0;
     }
     const char* scene_path = argv[1];
     int width = 800, height = 600, frames = 1, warmup = 0, batch = 0, device = 0;
     double spp = 4, depth = 5, exposure = 1.0, gamma = 2.2, denoise = 0;
     uint32_t seed = 1;
-    std::string aa = "supersampling", tone = "reinhard", precision = "f64", accel = "auto", out;
-    bool lights = false;
+    std::string aa = "supersampling", tone = "reinhard", precision = "f64", accel = "auto", out, aovs;
+    bool lights = false, guided = false;
+    rt_guided_params gp{RT_GUIDED_DEFAULT_LEVELS, 0, RT_GUIDED_DEFAULT_SIGMA_COLOR, RT_GUIDED_DEFAULT_SIGMA_ALBEDO,
+                        RT_GUIDED_DEFAULT_SIGMA_NORMAL, RT_GUIDED_DEFAULT_SIGMA_DEPTH};
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--lights") { lights = true; continue; }
+        if (a == "--guided") { guided = true; continue; }
         if (i + 1 >= argc) die("missing value for ", a.c_str());
         const char* v = argv[++i];
         if (a == "--width") width = atoi(v);
@@ -91,6 +109,13 @@ int main(int argc, char** argv) {
         else if (a == "--batch") batch = atoi(v);
         else if (a == "--device") device = atoi(v);
         else if (a == "--out") out = v;
+        else if (a == "--aovs") aovs = v;
+        else if (a == "--guided-levels") { gp.levels = atoi(v); guided = true; }
+        else if (a == "--guided-sigma") {
+            if (sscanf(v, "%lf,%lf,%lf,%lf", &gp.sigma_color, &gp.sigma_albedo, &gp.sigma_normal, &gp.sigma_depth) != 4)
+                die("--guided-sigma takes colour,albedo,normal,depth: ", v);
+            guided = true;
+        }
         else die("unknown option ", a.c_str());
     }
     if (frames < 1 || warmup < 0) die("--frames must be >= 1 and --warmup >= 0");
@@ -105,6 +130,7 @@ int main(int argc, char** argv) {
     if (!desc) die("--lights: ", rt_last_error());
     check(rt_scene_create(desc, device, &scene), "uploading the scene");
     const double upload_ms = now_ms() - t_up;
+    if (guided) check(rt_scene_set_guided(scene, &gp), "--guided");
 
     rt_settings s{};
     s.width = width;
@@ -162,6 +188,14 @@ int main(int argc, char** argv) {
             fwrite(rgb.data(), 1, rgb.size(), f);
         }
         fclose(f);
+    }
+    if (!aovs.empty()) {
+        std::vector<float> albedo(3 * n), normal(3 * n), zdepth(n);
+        rt_aov_output ao{albedo.data(), normal.data(), zdepth.data(), nullptr, nullptr};
+        check(rt_aovs(scene, &s, &ao), "--aovs");
+        write_pfm(aovs + ".albedo.pfm", albedo.data(), width, height, 3);
+        write_pfm(aovs + ".normal.pfm", normal.data(), width, height, 3);
+        write_pfm(aovs + ".depth.pfm", zdepth.data(), width, height, 1);
     }
     rt_scene_destroy(scene);
     rt_json_scene_destroy(js);

@@ -66,7 +66,34 @@ export function settingsOf(rt, opts = {}) {
         denoise: rt.denoising ? 1 : 0,
         denoiseW1: Math.exp(-(1) / (2 * rt.denoiseStrength * rt.denoiseStrength)),
         denoiseW2: Math.exp(-(2) / (2 * rt.denoiseStrength * rt.denoiseStrength)),
+        // the edge-aware guided filter over the linear mean (opt-in): the RayTracer's own members (GpuRayTracer),
+        // else the options (installGpuRender on a reference RayTracer); unset parameters take the library's defaults
+        ...guidedOf(rt, opts),
     };
+}
+
+function guidedOf(rt, opts) {
+    const pick = (member, option) => (rt[member] !== undefined ? rt[member] : opts[option]);
+    const g = { guided: pick('guidedDenoise', 'guidedDenoise') ? 1 : 0 };
+    for (const [member, key] of [['guidedLevels', 'guidedLevels'], ['guidedSigmaColor', 'guidedSigmaColor'],
+        ['guidedSigmaAlbedo', 'guidedSigmaAlbedo'], ['guidedSigmaNormal', 'guidedSigmaNormal'], ['guidedSigmaDepth', 'guidedSigmaDepth']]) {
+        const v = pick(member, key);
+        if (v !== undefined) g[key] = v;
+    }
+    return g;
+}
+
+// The feature buffers of the primary hit (albedo, normal: Float32Array of 3 per pixel; depth: Float32Array; kind,
+// index: Int32Array), top-down row-major: one pinhole ray through every pixel centre, no random numbers.
+export function gpuAovs(rt, opts = {}) {
+    const nat = loadNative();
+    const lit = rt.directLighting !== undefined ? !!rt.directLighting : !!opts.directLighting;
+    const scene = residentScene(rt, nat, opts.device || 0, lit);
+    return nat.aovs(scene, {
+        width: rt.width, height: rt.height, precision: PRECISION[opts.precision || 'f64'], accel: ACCEL[opts.accel || 'auto'],
+        cropX0: opts.crop ? opts.crop[0] : 0, cropY0: opts.crop ? opts.crop[1] : 0,
+        cropW: opts.crop ? opts.crop[2] : 0, cropH: opts.crop ? opts.crop[3] : 0,
+    });
 }
 
 // Progress granularity.  The reference reports progress and repaints after every row
@@ -209,6 +236,7 @@ export class GpuRayTracer {
         this.toneMapping = 'reinhard'; this.antiAliasing = 'supersampling';
         this.denoising = false; this.denoiseStrength = 0.5;
         this.directLighting = !!opts.directLighting;                // opt-in: render world.lights
+        this.guidedDenoise = !!opts.guidedDenoise;                  // opt-in: the guided filter (INTEGRATION.md)
         const d = defaultScene(this.width, this.height, permutation(opts.seed || 0));
         this.world = d.world;
         this.camera = d.camera;
@@ -244,6 +272,10 @@ export class GpuRayTracer {
         this.denoising = p.denoising || false;
         this.denoiseStrength = p.denoiseStrength || 0.5;
         if (p.directLighting !== undefined) this.directLighting = !!p.directLighting;   // (not a reference setting)
+        // the guided filter's keys, read only when present (not reference settings either)
+        if (p.guidedDenoise !== undefined) this.guidedDenoise = !!p.guidedDenoise;
+        for (const k of ['guidedLevels', 'guidedSigmaColor', 'guidedSigmaAlbedo', 'guidedSigmaNormal', 'guidedSigmaDepth'])
+            if (p[k] !== undefined) this[k] = p[k];
     }
 
     updateBackground(type, intensity = 1.0) {                        // ray-tracer.js:568-585
@@ -270,6 +302,11 @@ export class GpuRayTracer {
         blit(this, res);
         this.lastStats = res.stats;
         if (onProgress) onProgress(1.0);
+    }
+
+    // The feature buffers of the primary hit as Float32Arrays (gpuAovs); opts.crop: [x0, y0, w, h]
+    renderAovs(opts = {}) {
+        return gpuAovs(this, { ...this.opts, ...opts });
     }
 
     // Everything render() computes, plus diagnostics (linear mean, per-pixel segments / draws).

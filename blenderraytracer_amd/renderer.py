@@ -52,6 +52,11 @@ def settings_struct(width, height, samples, max_bounces, anti_aliasing, tone_map
     return s
 
 
+# the guided filter's defaults (DESIGN.md §4 "Guided filter": the sweep that chose the sigmas)
+GUIDED_LEVELS = capi.RT_GUIDED_DEFAULT_LEVELS
+GUIDED_SIGMAS = dict(capi.RT_GUIDED_DEFAULT_SIGMAS)
+
+
 class GpuRayTracer:
     def __init__(self, width, height, seed=0, device=0, precision=capi.RT_PREC_F64, accel=capi.RT_ACCEL_AUTO,
                  sum_order=capi.RT_SUM_POOL, direct_lighting=False):
@@ -65,6 +70,10 @@ class GpuRayTracer:
         self.max_bounces, self.samples, self.gamma, self.exposure = 5, 4, 2.2, 1.0
         self.tone_mapping, self.anti_aliasing = "reinhard", "supersampling"
         self.denoising, self.denoise_strength = False, 0.5
+        # the edge-aware guided filter over the linear mean (opt-in)
+        self.guided_denoise, self.guided_levels = False, GUIDED_LEVELS
+        self.guided_sigma_color, self.guided_sigma_albedo = GUIDED_SIGMAS["color"], GUIDED_SIGMAS["albedo"]
+        self.guided_sigma_normal, self.guided_sigma_depth = GUIDED_SIGMAS["normal"], GUIDED_SIGMAS["depth"]
         self.world, self.camera = default_scene(self.width, self.height, keyed_permutation(seed))
         self.image_data = np.zeros((self.height, self.width, 4), dtype=np.uint8)
         self.float_data = None
@@ -108,6 +117,15 @@ class GpuRayTracer:
         if "directLighting" in params and bool(truthy(g("directLighting"))) != self.direct_lighting:
             self.direct_lighting = not self.direct_lighting
             self._dirty = True                      # the lights are part of the scene on the device
+        # the guided filter's keys, read only when present: a dict without them leaves the filter as it was
+        if "guidedDenoise" in params:
+            self.guided_denoise = bool(truthy(g("guidedDenoise")))
+        if "guidedLevels" in params:
+            self.guided_levels = int(g("guidedLevels"))
+        for key, attr in (("guidedSigmaColor", "guided_sigma_color"), ("guidedSigmaAlbedo", "guided_sigma_albedo"),
+                          ("guidedSigmaNormal", "guided_sigma_normal"), ("guidedSigmaDepth", "guided_sigma_depth")):
+            if key in params:
+                setattr(self, attr, float(g(key)))
 
     def update_background(self, type, intensity=1.0):
         self.world.sky_intensity = intensity
@@ -139,9 +157,38 @@ class GpuRayTracer:
             self._dirty = False
         return self._scene
 
+    def guided_params(self):
+        """rt_guided_params of the current settings (None: the filter is off)."""
+        if not self.guided_denoise:
+            return None
+        return capi.GuidedParams(int(self.guided_levels), 0, float(self.guided_sigma_color), float(self.guided_sigma_albedo),
+                                 float(self.guided_sigma_normal), float(self.guided_sigma_depth))
+
+    def _apply_guided(self, lib, scene):
+        p = self.guided_params()
+        capi.check(lib.rt_scene_set_guided(scene, None if p is None else C.byref(p)))
+
+    def render_aovs(self, crop=None):
+        """The feature buffers of the primary hit (rt_aovs): albedo and normal (h, w, 3), depth (h, w) as float32,
+        kind and index (h, w) as rt_closest_hits reports them.  One pinhole ray through every pixel centre; no
+        random numbers, so the buffers are noise-free whatever the sample count."""
+        lib = capi.load_library()
+        scene = self.scene_handle()
+        st = self.settings(crop=crop)
+        cw, ch = st.crop_w or self.width, st.crop_h or self.height
+        res = {"albedo": np.zeros((ch, cw, 3), dtype=np.float32), "normal": np.zeros((ch, cw, 3), dtype=np.float32),
+               "depth": np.zeros((ch, cw), dtype=np.float32), "kind": np.zeros((ch, cw), dtype=np.int32),
+               "index": np.zeros((ch, cw), dtype=np.int32)}
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        out = capi.AovOutput(res["albedo"].ctypes.data_as(fp), res["normal"].ctypes.data_as(fp),
+                             res["depth"].ctypes.data_as(fp), res["kind"].ctypes.data_as(ip), res["index"].ctypes.data_as(ip))
+        capi.check(lib.rt_aovs(scene, C.byref(st), C.byref(out)))
+        return res
+
     def render(self, on_progress=None, crop=None, want=("rgba8",), batch_samples=0, resume=None, devices=None):
         """RayTracer.render: fills image_data (RGBA8) and float_data (post-gamma RGBA float).
-        Returns a dict of the requested host arrays (mean, post, rgba8, segments, draws, preview).
+        Returns a dict of the requested host arrays (mean, post, rgba8, segments, draws, preview, and the
+        feature buffers albedo, normal, depth of render_aovs).
         resume: a checkpoint() result to continue from (rt_render_resume).
         devices: HIP ordinals to deal the sample batches to (multi-GPU; may repeat a device).
         "preview" in want (with batch_samples): when on_progress runs, image_data (full frame) and the
@@ -150,6 +197,7 @@ class GpuRayTracer:
         there and raises RuntimeError(RT_ERR_CANCELLED)."""
         lib = capi.load_library()
         scene = self.scene_handle()
+        self._apply_guided(lib, scene)
         st = self.settings(crop=crop, batch_samples=batch_samples, devices=devices)
         cw = st.crop_w or self.width
         ch = st.crop_h or self.height
@@ -191,6 +239,9 @@ class GpuRayTracer:
         if crop is None:
             self.image_data = res["rgba8"]
             self.float_data = res["post"]
+        if any(k in want for k in ("albedo", "normal", "depth")):
+            aov = self.render_aovs(crop=crop)
+            res.update({k: aov[k] for k in ("albedo", "normal", "depth") if k in want})
         if on_progress:
             on_progress(1.0)
         assert n == res["rgba8"].shape[0] * res["rgba8"].shape[1]

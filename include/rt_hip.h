@@ -400,6 +400,55 @@ int rt_texture_values(rt_scene* scene, int32_t precision, int32_t texture, const
  * hit; they differ in speed only. */
 int rt_scene_walk(rt_scene* scene, int32_t precision, int32_t accel);
 
+/* Feature buffers and the guided denoiser: an append-only extension of generation 3 (RT_ABI_VERSION and every
+ * struct above stay as they are).
+ *
+ * Feature buffers (AOVs) of the primary hit: one ray per pixel through the pixel centre (the RT_AA_CENTER
+ * formula) from a pinhole (lens offset zero), so no random number is drawn; the closest hit is the trace
+ * kernels' own query (rt_closest_hits).  Per pixel: albedo (Lambertian / Metal: the albedo, a textured
+ * material's texture value at the hit point — in RT_PREC_F32 with the textures' sines taken from the binary64
+ * sine rounded to binary32, so the buffer is the same bits on every device and host, within an ulp or two of
+ * the value the binary32 trace kernels use; Dielectric (1, 1, 1); Emissive min(emission, 1) per channel),
+ * the hit record's normal (facing the ray) and depth = t |d|; a miss gives albedo and normal 0 and depth
+ * +inf.  Computed in the settings' precision, stored as binary32.  Only width, height, the crop window,
+ * precision and accel of the settings are read. */
+#define RT_GUIDED_MAX_LEVELS 8
+/* the hosts' defaults (chosen by the sweep of DESIGN.md §4 "Guided filter") */
+#define RT_GUIDED_DEFAULT_LEVELS 5
+#define RT_GUIDED_DEFAULT_SIGMA_COLOR 1.0
+#define RT_GUIDED_DEFAULT_SIGMA_ALBEDO 0.1
+#define RT_GUIDED_DEFAULT_SIGMA_NORMAL 0.35
+#define RT_GUIDED_DEFAULT_SIGMA_DEPTH 0.05
+typedef struct rt_guided_params {
+    int32_t levels, _pad;      /* 1 .. RT_GUIDED_MAX_LEVELS à-trous levels (step 1, 2, 4, ...) */
+    double sigma_color, sigma_albedo, sigma_normal, sigma_depth;   /* each > 0; +inf switches the term off */
+} rt_guided_params;
+/* Host outputs of rt_aovs, each optional (NULL = not wanted); n = crop pixels, top-down row-major. */
+typedef struct rt_aov_output {
+    float* albedo;             /* n*3 */
+    float* normal;             /* n*3 */
+    float* depth;              /* n */
+    int32_t* kind;             /* n: as rt_closest_hits reports it (-1 none) */
+    int32_t* index;            /* n: likewise */
+} rt_aov_output;
+int rt_aovs(rt_scene* scene, const rt_settings* settings, const rt_aov_output* out);
+/* The same on device: d_guides (n x 8 floats, 16-byte aligned) = albedo[3], normal[3], depth, 0 per pixel, the
+ * guide records rt_guided_filter_device reads.  Asynchronous on hip_stream. */
+int rt_aovs_device(rt_scene* scene, const rt_settings* settings, float* d_guides, void* hip_stream);
+/* The guided filter (edge-avoiding à-trous wavelet filter): d_color (width x height x 3 binary64,
+ * the linear mean) filtered along d_guides into d_out, always in binary64; d_color is not written and d_out
+ * must not overlap it.  The intermediate levels ping-pong between d_out and one scratch frame the scene owns.
+ * Non-finite pixels pass through unchanged and are never averaged into others.  Asynchronous on hip_stream. */
+int rt_guided_filter_device(rt_scene* scene, int32_t width, int32_t height, const rt_guided_params* params,
+                            const double* d_color, const float* d_guides, double* d_out, void* hip_stream);
+/* NULL = off (the default).  While set, the final epilogue of rt_render / rt_render_resume and
+ * rt_finalize_device filter the mean (sum / samples) along the guides of the settings' frame before tone
+ * mapping: rt_output.mean is the filtered mean and post / rgba8 are made from it (the Gaussian `denoise`, if
+ * also on, runs after it).  Like `denoise` it needs the full frame (RT_ERR_INVALID for a crop).  Running
+ * preview frames are not filtered, and the scene's sums are never overwritten: checkpoints and resumes are
+ * unchanged.  The parameters are validated before any device is touched (RT_ERR_INVALID). */
+int rt_scene_set_guided(rt_scene* scene, const rt_guided_params* params);
+
 /* Request cancellation of an in-flight rt_render on `scene` (the pool kernels read it between items;
  * see rt_render). */
 int rt_cancel(rt_scene* scene);
