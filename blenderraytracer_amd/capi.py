@@ -140,6 +140,11 @@ EXPORTS = {
     "rt_guided_filter_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GuidedParams), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "rt_scene_set_guided": (C.c_int, [C.c_void_p, C.POINTER(GuidedParams)]),
+    "rt_scene_set_emitter_sampling": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rt_scene_emitter_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "rt_emitter_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
+                                     C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
     # include/rt_scene_json.h (host-only scene-JSON loader)
     "rt_json_scene_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_json_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),

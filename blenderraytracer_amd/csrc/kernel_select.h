@@ -182,15 +182,16 @@ struct SceneFacts {
     int num_lights, num_tex, num_tri_nodes, num_tri_wide, num_sphere_wide, num_grid_cells, use_grid, num_planes,
         num_boxes, background, cam_ortho, stack_entries, num_mats;
     size_t grid_lds_bytes;         // the grid's LDS copy in this precision (pt_core.h grid_lds_bytes)
+    int num_emitters;              // listed emitters of a render with emitter sampling
 };
 template <class R>
 SceneFacts scene_facts(const SceneView<R>& sc) {
     return SceneFacts{sc.num_lights, sc.num_tex, sc.num_tri_nodes, sc.num_tri_wide, sc.num_sphere_wide, sc.num_grid_cells,
                       sc.use_grid, sc.num_planes, sc.num_boxes, sc.background, sc.cam_ortho, sc.stack_entries,
-                      sc.num_mats, grid_lds_bytes(sc)};
+                      sc.num_mats, grid_lds_bytes(sc), sc.num_emitters};
 }
 
-constexpr int kAccelCount = ACC_BVH_STACK_LIT + 1;
+constexpr int kAccelCount = ACC_BVH_STACK_NEE + 1;
 // the kernels of trace_pool_lds_kernel (persistent multi-wave workgroups taking items from a queue, their
 // walk's data staged in LDS); every other mode is a one-wave kernel
 constexpr bool lds_form(int acc) {
@@ -203,7 +204,7 @@ constexpr int plain_of(int acc) {
 }
 // rt_scene_walk's answer: 0 World order, 1 a tree, 2 the uniform grid
 constexpr int walk_report(int acc) {
-    return acc == ACC_BRUTE || acc == ACC_BRUTE_LEAN || acc == ACC_BRUTE_TEX || acc == ACC_BRUTE_LIT ? 0
+    return acc == ACC_BRUTE || acc == ACC_BRUTE_LEAN || acc == ACC_BRUTE_TEX || acc == ACC_BRUTE_LIT || acc == ACC_BRUTE_NEE ? 0
          : acc == ACC_GRID || acc == ACC_GRID_LDS || acc == ACC_GRID_LDS_LEAN ? 2 : 1;
 }
 
@@ -226,8 +227,9 @@ auto with_acc(int acc, F&& f) -> decltype(f(std::integral_constant<int, 0>{})) {
 template <class R>
 KernelChoice select_kernel(const SceneFacts& s, int aa_mode, bool bvh, bool pool, const SelectKnobs& k) {
     const auto one_wave = [](Accel acc) { return KernelChoice{acc, false, 0, 0}; };
-    // direct lighting, then procedural textures: the F_LIGHT / F_TEX kernels (World order and the general
-    // ordered walk, one-wave forms only), whatever the walk choice and the knobs
+    // emitter sampling, direct lighting, then procedural textures: the F_NEE / F_LIGHT / F_TEX kernels (World
+    // order and the general ordered walk, one-wave forms only), whatever the walk choice and the knobs
+    if (s.num_emitters > 0) return one_wave(bvh ? ACC_BVH_STACK_NEE : ACC_BRUTE_NEE);
     if (s.num_lights > 0) return one_wave(bvh ? ACC_BVH_STACK_LIT : ACC_BRUTE_LIT);
     if (s.num_tex > 0) return one_wave(bvh ? ACC_BVH_STACK_TEX : ACC_BRUTE_TEX);
     // the lean form of a kernel compiled for the primitives `feat`

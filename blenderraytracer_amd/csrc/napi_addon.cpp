@@ -2,7 +2,8 @@
 //
 // The JS host (blenderraytracer_amd/js/gpu-ray-tracer.mjs) keeps the reference's RayTracer surface
 // and calls into this addon for the part under RayTracer.render (js/ray-tracer.js:166-281):
-//   createScene(desc, device)          -> External   (rt_scene_create: scene copied into HBM)
+//   createScene(desc, device, emitterSampling) -> External   (rt_scene_create: scene copied into HBM;
+//                                         emitterSampling != 0: rt_scene_set_emitter_sampling)
 //   render(scene, settings, progress?) -> Promise<{mean?, post?, rgba8, segments?, draws?, stats}>
 //                                         (rt_render on a libuv worker thread: the event loop stays live)
 //   cancel(scene)                      -> rt_cancel (the queued batches stop at their next item)
@@ -144,15 +145,16 @@ SceneBox* get_box(napi_env env, napi_value v) {
     return static_cast<SceneBox*>(p);
 }
 
-// createScene(desc, device): desc holds the rt_scene_desc records as typed arrays (layout: rt_hip.h)
+// createScene(desc, device, emitterSampling): desc holds the rt_scene_desc records as typed arrays (layout: rt_hip.h)
 napi_value create_scene(napi_env env, napi_callback_info info) {
-    size_t argc = 2;
-    napi_value argv[2];
+    size_t argc = 3;
+    napi_value argv[3];
     NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
-    if (argc < 1) return throw_err(env, "createScene(desc, device)");
+    if (argc < 1) return throw_err(env, "createScene(desc, device, emitterSampling)");
     napi_value d = argv[0];
-    int32_t device = 0;
+    int32_t device = 0, emitters = 0;
     if (argc > 1) napi_get_value_int32(env, argv[1], &device);
+    if (argc > 2) napi_get_value_int32(env, argv[2], &emitters);
     rt_scene_desc desc;
     std::memset(&desc, 0, sizeof desc);
     desc.abi_version = RT_ABI_VERSION;
@@ -214,6 +216,10 @@ napi_value create_scene(napi_env env, napi_callback_info info) {
     }
     rt_scene* sc = nullptr;
     if (rt_scene_create(&desc, device, &sc) != RT_OK) return throw_err(env, std::string("rt_scene_create: ") + rt_last_error());
+    if (emitters && rt_scene_set_emitter_sampling(sc, 1) != RT_OK) {        // sample the scene's emissive geometry
+        rt_scene_destroy(sc);
+        return throw_err(env, std::string("rt_scene_set_emitter_sampling: ") + rt_last_error());
+    }
     SceneBox* box = new SceneBox();
     box->sc = sc;
     napi_value ext;

@@ -252,6 +252,14 @@ template <class R> struct TexView { const TexRec<R>* recs; const int* perms; con
 enum LightType : int { LIGHT_POINT = 0, LIGHT_DIRECTIONAL = 1 };
 template <class R> struct LightRec { int type, pad; R v[3]; R color[3]; R intensity; };
 template <class R> struct LightView { const LightRec<R>* recs; int num, pad; };
+// Emitter sampling (F_NEE): one record per listed emitter — an Emissive sphere or triangle — in World.objects
+// order (scene_pack.h build_emitters), holding all that sampling it needs.  g: a sphere's {cx, cy, cz, r2}, a
+// triangle's TriRec words {v0, e1, e2, n}; le: the emission; area: a triangle's |e1 x e2| / 2 (0 for a sphere).
+// The EmitterView follows the LightView behind `perm` (emitter_view).  A hit recognises a listed primitive
+// without a search: sphere_listed[i] != 0, tri_area[i] > 0 (the area the record holds, 0 for the unlisted).
+enum EmitterKind : int { EMIT_SPHERE = 0, EMIT_TRI = 1 };
+template <class R> struct EmitterRec { int kind, idx; R g[12]; R le[3]; R area; };
+template <class R> struct EmitterView { const EmitterRec<R>* recs; const int* sphere_listed; const R* tri_area; int num, pad; };
 
 template <class R>
 struct SceneView {
@@ -298,6 +306,8 @@ struct SceneView {
     int stack_entries;             // deepest leaf of the two trees (>= 1): the ordered walk's stack bound
     const SphereLeaf<R>* big_spheres;   // dominant spheres kept out of the sphere tree (scene_pack.h)
     int num_big_spheres;
+    int num_emitters;              // listed emitters of a render with emitter sampling (0: none; only then do the
+                                   // F_NEE kernels run).  Like num_tex and num_lights it fills 4 padding bytes
     // uniform grid over the sphere tree's spheres (ACC_GRID, scene_pack.h build_grid): cell c = (x, y, z)
     // -> x + n0 (y + n1 z) holds grid_leaf[grid_cell[c] .. grid_cell[c + 1])
     const int* grid_cell;
@@ -336,6 +346,15 @@ static_assert(sizeof(TexView<double>) == 32 && sizeof(TexView<float>) == 32, "Te
 constexpr int kLightViewAt = kTexViewAt + 8;
 template <class R> RT_HD const LightView<R>* light_view(const SceneView<R>& sc) {
     return reinterpret_cast<const LightView<R>*>(sc.perm + kLightViewAt);
+}
+// num_emitters sits in padding as well, and the EmitterView follows the LightView (zeros, num = 0, in a scene
+// whose emitters are sampled and whose lights are not)
+static_assert(offsetof(SceneView<double>, grid_cell) == offsetof(SceneView<double>, num_big_spheres) + 8 &&
+              offsetof(SceneView<float>, grid_cell) == offsetof(SceneView<float>, num_big_spheres) + 8, "num_emitters fills padding");
+static_assert(sizeof(LightView<double>) == 16 && sizeof(LightView<float>) == 16, "LightView in 4 ints");
+constexpr int kEmitterViewAt = kLightViewAt + 4;
+template <class R> RT_HD const EmitterView<R>* emitter_view(const SceneView<R>& sc) {
+    return reinterpret_cast<const EmitterView<R>*>(sc.perm + kEmitterViewAt);
 }
 
 enum HitKind : int { HIT_NONE = -1, HIT_SPHERE = 0, HIT_PLANE = 1, HIT_BOX = 2, HIT_TRI = 3 };
@@ -499,7 +518,8 @@ RT_HD bool sphere_filter_pass(const SphereFilter& s, const FilterRay& r) {
 // that code reads, so fewer scalars stay live across the segment loop (SGPR spills).
 enum Feat : int { F_PLANES = 1, F_BOXES = 2, F_TRIS = 4, F_BGALL = 8, F_CAMALL = 16, F_ALL = 31,
                   F_TEX = 32,     // F_TEX: textured Lambertian / Metal (not part of F_ALL: a kernel of its own)
-                  F_LIGHT = 64 }; // F_LIGHT: direct lighting from the scene's lights (kernels of their own, with F_TEX)
+                  F_LIGHT = 64,   // F_LIGHT: direct lighting from the scene's lights (kernels of their own, with F_TEX)
+                  F_NEE = 128 };  // F_NEE: emitter sampling with MIS (kernels of their own, with F_TEX and F_LIGHT)
 
 // Closest hit over the whole world: World.hit (world.js:20-33) with every object's hit() inlined.
 // All lanes walk the same primitive list in the same order, so every record load — including the
@@ -1333,13 +1353,15 @@ RT_HD Closest<R> closest_hit_grid(const SceneView<R>& sc, V3<R> o, V3<R> d, Work
 enum Accel : int { ACC_BRUTE = 0, ACC_BRUTE_LEAN = 1, ACC_BVH = 2, ACC_BVH_STACK = 3, ACC_BVH_SPHERES = 4, ACC_BVH_SPHERES_LDS = 5,
                    ACC_GRID = 6, ACC_GRID_LDS = 7, ACC_BVH_TRI_LDS = 8, ACC_GRID_LDS_LEAN = 9,
                    ACC_BVH_STACK_LEAN = 10, ACC_BRUTE_TEX = 11, ACC_BVH_STACK_TEX = 12,
-                   ACC_BRUTE_LIT = 13, ACC_BVH_STACK_LIT = 14 };
+                   ACC_BRUTE_LIT = 13, ACC_BVH_STACK_LIT = 14, ACC_BRUTE_NEE = 15, ACC_BVH_STACK_NEE = 16 };
 // ACC_BRUTE_LIT / ACC_BVH_STACK_LIT: the same two walks for renders with direct lighting (F_ALL | F_TEX |
 // F_LIGHT: a textured lit scene needs no third variant)
-// the walk a mode runs (the textured and lit modes walk like their plain twins)
+// ACC_BRUTE_NEE / ACC_BVH_STACK_NEE: the same two walks for renders that sample the scene's emitters (F_ALL |
+// F_TEX | F_LIGHT | F_NEE: textures, scene lights or both need no further variant)
+// the walk a mode runs (the textured, lit and emitter-sampling modes walk like their plain twins)
 template <int ACC> constexpr int walk_of() {
-    return ACC == ACC_BRUTE_TEX || ACC == ACC_BRUTE_LIT ? ACC_BRUTE
-         : ACC == ACC_BVH_STACK_TEX || ACC == ACC_BVH_STACK_LIT ? ACC_BVH_STACK : ACC;
+    return ACC == ACC_BRUTE_TEX || ACC == ACC_BRUTE_LIT || ACC == ACC_BRUTE_NEE ? ACC_BRUTE
+         : ACC == ACC_BVH_STACK_TEX || ACC == ACC_BVH_STACK_LIT || ACC == ACC_BVH_STACK_NEE ? ACC_BVH_STACK : ACC;
 }
 // The lean kernels (kernel_select.h select_kernel): compiled for the common scene shapes only, the sky
 // gradient, the perspective camera and supersampling AA —
@@ -1349,7 +1371,8 @@ template <int ACC> constexpr int walk_of() {
 template <int ACC> constexpr int feat_of() {
     return ACC == ACC_GRID_LDS_LEAN ? 0 : ACC == ACC_BVH_STACK_LEAN ? (F_PLANES | F_TRIS)
          : ACC == ACC_BRUTE_LEAN ? F_PLANES : ACC == ACC_BRUTE_TEX || ACC == ACC_BVH_STACK_TEX ? (F_ALL | F_TEX)
-         : ACC == ACC_BRUTE_LIT || ACC == ACC_BVH_STACK_LIT ? (F_ALL | F_TEX | F_LIGHT) : F_ALL;
+         : ACC == ACC_BRUTE_LIT || ACC == ACC_BVH_STACK_LIT ? (F_ALL | F_TEX | F_LIGHT)
+         : ACC == ACC_BRUTE_NEE || ACC == ACC_BVH_STACK_NEE ? (F_ALL | F_TEX | F_LIGHT | F_NEE) : F_ALL;
 }
 
 // RT_SC_RELOAD (bit mask of lean kernels: 1 tree, 2 grid, 4 brute force; default 2): the closest-hit
@@ -1735,6 +1758,95 @@ __host__ __device__ RT_COLD V3<R> texture_value(const TexView<R>* tv, int tex, V
     const R rings = js_sin<R>(s * sqrt(p.x * p.x + p.z * p.z) + grain * (R)10);
     const R m = (R)0.5 * ((R)1 + rings), w = (R)1 - m;
     return mk<R>((R)0.8 * m + (R)0.4 * w, (R)0.5 * m + (R)0.2 * w, (R)0.2 * m + (R)0.1 * w);
+}
+
+// ---- emitter sampling (F_NEE; INTEGRATION.md §10 fixes every operation and its order) -----------------
+// 1 - cos(theta_max) of the cone a sphere (r2) subtends from squared distance D2 > r2, without cancellation,
+// and the solid-angle density of the uniform cone sample, 1 / (2 pi (1 - cos theta_max))
+template <class R> RT_HD R sphere_cone_omc(R r2, R D2) {
+    const R q = r2 / D2;
+    return q / ((R)1 + sqrt((R)1 - q));
+}
+template <class R> RT_HD R cone_pdf(R omc) { return (R)1 / ((R)6.283185307179586 * omc); }
+// the density, per solid angle at the origin, of a triangle's uniform area sample at squared distance D2 seen
+// under |n_t . omega| = cl
+template <class R> RT_HD R tri_pdf(R D2, R cl, R area) { return D2 / (cl * area); }
+
+// One emitter sample from x with the stream ge: the emitter e = (u24 N) >> 24, a unit direction om towards it
+// and the direction's density pO per solid angle.  ok = false: no sample (x inside the sphere, the disk's
+// centre drawn, a triangle seen edge-on or from a point of itself); om and pO are then zero.
+// Only + - * / sqrt: the binary64 results are the same bits on the device, in the CPU build and in numpy.
+template <class R> struct EmitterDraw { int e; bool ok; V3<R> om; R pO; };
+template <class R>
+RT_HD EmitterDraw<R> sample_emitter(const EmitterView<R>* ev, int N, V3<R> x, Rng<R>& ge) {
+    EmitterDraw<R> s{0, false, mk<R>(0, 0, 0), (R)0};
+    s.e = (int)(((uint64_t)ge.next_u24() * (uint64_t)(uint32_t)N) >> 24);
+    const EmitterRec<R>& er = ev->recs[s.e];
+    if (er.kind == EMIT_SPHERE) {
+        const V3<R> w = mk(er.g[0], er.g[1], er.g[2]) - x;
+        const R D2 = dot(w, w), r2 = er.g[3];
+        if (!(D2 > r2)) return s;
+        const R omc = sphere_cone_omc(r2, D2);
+        const V3<R> ab = random_in_unit_disk(ge);
+        const R sq = ab.x * ab.x + ab.y * ab.y;
+        if (sq == (R)0) return s;
+        const R ct = (R)1 - sq * omc;
+        const R st = sqrt(js_max<R>((R)0, (R)1 - ct * ct));
+        const V3<R> wh = vdiv(w, sqrt(D2));
+        const V3<R> axis = fabs(wh.x) > (R)0.5 ? mk<R>(0, 1, 0) : mk<R>(1, 0, 0);
+        const V3<R> c1 = cross(axis, wh);
+        const V3<R> t1 = vdiv(c1, sqrt(dot(c1, c1)));
+        const V3<R> t2 = cross(wh, t1);
+        s.om = wh * ct + (t1 * ab.x + t2 * ab.y) * (st / sqrt(sq));
+        s.pO = cone_pdf(omc);
+        s.ok = true;
+        return s;
+    }
+    R u1 = ge.next(), u2 = ge.next();
+    if (u1 + u2 > (R)1) { u1 = (R)1 - u1; u2 = (R)1 - u2; }
+    const V3<R> y = (mk(er.g[0], er.g[1], er.g[2]) + mk(er.g[3], er.g[4], er.g[5]) * u1) + mk(er.g[6], er.g[7], er.g[8]) * u2;
+    const V3<R> v = y - x;
+    const R D2 = dot(v, v);
+    if (!(D2 > (R)0)) return s;
+    const V3<R> om = vdiv(v, sqrt(D2));
+    const R cl = fabs(dot(mk(er.g[9], er.g[10], er.g[11]), om));
+    if (!(cl > (R)0)) return s;
+    s.om = om;
+    s.pO = tri_pdf(D2, cl, er.area);
+    s.ok = true;
+    return s;
+}
+
+// The sampled primitive's own candidate test on the ray (x, om): the closest-hit query's sphere / triangle test
+// with tmin = 0.001.  false: the path tracer's own test would not hit it from here in this direction.
+template <class R>
+RT_HD bool emitter_candidate(const EmitterRec<R>& er, V3<R> x, V3<R> om, R& t) {
+    const R tmin = (R)0.001;
+    if (er.kind == EMIT_SPHERE)
+        return sphere_candidate(SphereRec<R>{er.g[0], er.g[1], er.g[2], er.g[3]}, x, om, dot(om, om), tmin, t);
+    const TriGeom<R> tg{er.g[0], er.g[1], er.g[2], er.g[3], er.g[4], er.g[5], er.g[6], er.g[7], er.g[8]};
+    return triangle_candidate(tg, x, om, tmin, t);
+}
+
+// What rt_emitter_samples reports of one query (x, n, key): the sample, its density p_l = pO / N, the
+// candidate's t_e and whether the emitter is seen.  Stages not reached leave zeros: no sample -> om = p_l = 0;
+// n . om <= 0 or no candidate -> t_e = 0, not visible.
+template <class R> struct EmitterQuery { int e; V3<R> om; R p_l, t_e; bool visible; };
+template <class R, int ACC>
+RT_HD EmitterQuery<R> emitter_query(const SceneView<R>& sc, V3<R> x, V3<R> n, uint32_t key, Work& w, BvhStack stk) {
+    const EmitterView<R>* ev = emitter_view(sc);
+    const int N = sc.num_emitters;
+    Rng<R> ge{key, 0};
+    const EmitterDraw<R> s = sample_emitter(ev, N, x, ge);
+    EmitterQuery<R> q{s.e, s.om, (R)0, (R)0, false};
+    if (!s.ok) return q;
+    q.p_l = s.pO / (R)N;
+    if (!(dot(n, s.om) > (R)0)) return q;
+    R t;
+    if (!emitter_candidate(ev->recs[s.e], x, s.om, t)) return q;
+    q.t_e = t;
+    q.visible = !occluded<R, ACC>(sc, x, s.om, t, w, stk);
+    return q;
 }
 
 }  // namespace rt

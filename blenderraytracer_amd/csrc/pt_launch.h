@@ -129,6 +129,13 @@ template <class R>
 hipError_t launch_occluded(const SceneView<R>& sc, bool bvh, const double* rays, const double* tmax, size_t n,
                            uint8_t* out, hipStream_t stream);
 
+// emitter_query of n queries (points: n x 6 doubles x, n; keys: n words; device) -> out (n x 5 doubles: omega,
+// p_l, t_e) and ev (n x 2 ints: emitter, visible), device: rt_emitter_samples, the emitter-sampling kernels' own
+// sample.  The scene must list emitters (sc.num_emitters > 0)
+template <class R>
+hipError_t launch_emitter_samples(const SceneView<R>& sc, bool bvh, const double* points, const uint32_t* keys, size_t n,
+                                  double* out, int* ev, hipStream_t stream);
+
 // Texture.value of texture `tex` at n points (n x 3 doubles, device) -> rgb (n x 3 doubles, device):
 // rt_texture_values.  The scene must have textures (sc.tex), tex in [0, num_textures)
 template <class R>

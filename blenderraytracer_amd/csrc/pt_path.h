@@ -279,6 +279,70 @@ RT_HD V3<R> direct_light(const SceneView<R>& sc, const Hit<R>& h, V3<R> att, Wor
     return direct;
 }
 
+// Emitter sampling at a Lambertian / TexturedLambertian hit (F_NEE): one emitter drawn
+// uniformly from the scene's list, one direction towards it (sample_emitter), the cosine against the facing
+// normal, the sampled primitive's own candidate test and a shadow ray up to its t (occluded), weighted against
+// the scattered ray's density cs / pi by the balance heuristic:
+//   direct = (att (.) Le) * ((cs / pi) / (p_l + p_b)),  p_l = pO / N,  p_b = cs / pi.
+// The draws come from a stream of their own, keyed by the sample's key and the bounce: the path's g.k, its
+// decisions and its counters are the plain render's.
+#ifndef RT_NEE_MUTATION
+#define RT_NEE_MUTATION 0         // tests/hostcheck only: 1 = emission weight forced to 1, 2 = hit-side p_l without 1 / N
+#endif
+template <class R, int ACC>
+RT_HD V3<R> emitter_light(const SceneView<R>& sc, const Hit<R>& h, V3<R> att, uint32_t key, int bounce, Work& w, BvhStack stk) {
+    const V3<R> none = mk<R>(0, 0, 0);
+    const EmitterView<R>* ev = emitter_view(sc);
+    const int N = sc.num_emitters;
+    if (N <= 0) return none;
+    Rng<R> ge{lowbias32(key ^ lowbias32((uint32_t)bounce + 0x4E454531u)), 0};
+    const EmitterDraw<R> s = sample_emitter(ev, N, h.p, ge);
+    if (!s.ok) return none;
+    const R cs = dot(h.n, s.om);
+    if (!(cs > (R)0)) return none;
+    const EmitterRec<R>& er = ev->recs[s.e];
+    R te;
+    if (!emitter_candidate(er, h.p, s.om, te)) return none;
+    if (occluded<R, ACC>(sc, h.p, s.om, te, w, stk)) return none;
+    const R pb = cs / (R)3.141592653589793;
+    const R f = pb / (s.pO / (R)N + pb);
+    return mk((att.x * er.le[0]) * f, (att.y * er.le[1]) * f, (att.z * er.le[2]) * f);
+}
+
+// The density sample_emitter has, per solid angle at o, for the direction d that reached the listed emitter at
+// the closest hit c.  false: the primitive is not listed (boxes, planes, degenerate ones), or sampling from o
+// skips it (o inside the sphere).
+template <class R>
+RT_HD bool emitter_hit_pdf(const SceneView<R>& sc, const Closest<R>& c, V3<R> o, V3<R> d, R& pO) {
+    const EmitterView<R>* ev = emitter_view(sc);
+    if (c.kind == HIT_SPHERE) {
+        if (!ev->sphere_listed[c.idx]) return false;
+        const SphereRec<R> s = sc.spheres[c.idx];
+        const V3<R> w = mk(s.cx, s.cy, s.cz) - o;
+        const R D2 = dot(w, w);
+        if (!(D2 > s.r2)) return false;
+        pO = cone_pdf(sphere_cone_omc(s.r2, D2));
+        return true;
+    }
+    if (c.kind != HIT_TRI) return false;
+    const R area = ev->tri_area[c.idx];
+    if (!(area > (R)0)) return false;
+    const TriRec<R> tr = sc.tris[c.idx];
+    const R dd = dot(d, d);
+    pO = tri_pdf((c.t * c.t) * dd, fabs(dot(mk(tr.nx, tr.ny, tr.nz), d)) / sqrt(dd), area);
+    return true;
+}
+// The weight of the emission met by a scattered ray (o, d) at the closest hit c, whose direction a Lambertian
+// scatter drew with density pb: pb / (pb + pO / N), the balance heuristic against emitter_light; 1 after a camera
+// ray, a Metal or a Dielectric scatter (pb = 0; NaN too) and where emitter_hit_pdf has no density.
+template <class R>
+RT_HD R emission_weight(const SceneView<R>& sc, const Closest<R>& c, V3<R> o, V3<R> d, R pb) {
+    if (!(pb > (R)0) || RT_NEE_MUTATION == 1) return (R)1;
+    R pO;
+    if (!emitter_hit_pdf(sc, c, o, d, pO)) return (R)1;
+    return pb / (pb + (RT_NEE_MUTATION == 2 ? pO : pO / (R)sc.num_emitters));
+}
+
 // Shade the segment whose closest hit is c (rayColor's body after world.hit, ray-tracer.js:106-122):
 // emission / scatter / background.  Returns true when the sample's path ended; its radiance L is
 // then in `L`, otherwise (o, d, T, depth) describe the next segment.
@@ -289,9 +353,19 @@ RT_HD V3<R> direct_light(const SceneView<R>& sc, const Hit<R>& h, V3<R> att, Wor
 // count in, and the lane's traversal stack (idle while a segment is shaded).  One pointer, nullptr elsewhere:
 // further by-value parameters changed the register allocation of kernels that never use them.
 template <class R> struct LightCtx { V3<R> dsum; Work* w; BvhStack stk; };
+// F_NEE: the emitter-sampling kernels' context, handed on as its LightCtx — pb, the density of the direction the
+// last scatter drew (0: none — a camera ray, Metal, Dielectric), and the render's depth (the bounce index keys
+// the emitter draws).  A struct of its own: LightCtx with these two members changed the register allocation of
+// the binary32 lane-per-pixel lit kernels (2 and 1 VGPR spills fewer), and every existing kernel stays as it was.
+template <class R> struct NeeCtx : LightCtx<R> {
+    R pb;
+    int max_depth;
+    RT_HD NeeCtx(V3<R> d, Work* w, BvhStack s) : LightCtx<R>{d, w, s}, pb((R)0), max_depth(0) {}
+};
 // the kernels' LightCtx variable: an empty object in the instantiations without F_LIGHT
 struct NoLightCtx { template <class... A> RT_HD NoLightCtx(A&&...) {} };
-template <class R, bool LIT> using LightState = std::conditional_t<LIT, LightCtx<R>, NoLightCtx>;
+template <class R, bool LIT, bool NEE = false>
+using LightState = std::conditional_t<NEE, NeeCtx<R>, std::conditional_t<LIT, LightCtx<R>, NoLightCtx>>;
 template <class R, int FEAT = F_ALL, int ACC = ACC_BRUTE>
 RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, V3<R>& d, V3<R>& T, int& depth,
                          Rng<R>& g, V3<R>& L, const MatRec<R>* mats = nullptr, LightCtx<R>* lc = nullptr) {
@@ -313,6 +387,10 @@ RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, 
         if (m.type == 3) {                                                    // Emissive (materials.js:87-96)
             RT_HCOUNT(HC_EMISSIVE, 1);
             L = mk(T.x * m.c[0], T.y * m.c[1], T.z * m.c[2]);                 // emission
+            if constexpr ((FEAT & F_NEE) != 0) {                              // ... MIS-weighted against emitter sampling
+                const R wgt = emission_weight<R>(sc, c, o, d, static_cast<NeeCtx<R>*>(lc)->pb);
+                if (wgt != (R)1) L = L * wgt;
+            }
         } else {
             V3<R> nd, att;
             if (scatter<R, (FEAT & F_TRIS) != 0 && (FEAT & F_ALL) != F_ALL>(m, h, unit, p, g, nd, att)) {
@@ -330,6 +408,18 @@ RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, 
                     if (m.type == 0) {
                         const V3<R> dl = direct_light<R, ACC>(sc, h, att, *lc->w, lc->stk);
                         lc->dsum = lc->dsum + mk(T.x * dl.x, T.y * dl.y, T.z * dl.z);
+                    }
+                }
+                if constexpr ((FEAT & F_NEE) != 0) {
+                    NeeCtx<R>* nc = static_cast<NeeCtx<R>*>(lc);
+                    nc->pb = (R)0;
+                    if (m.type == 0) {
+                        // not at the last allowed bounce: its successor segment does not exist in the plain render
+                        if (depth > 1) {
+                            const V3<R> el = emitter_light<R, ACC>(sc, h, att, g.key, nc->max_depth - depth, *nc->w, nc->stk);
+                            nc->dsum = nc->dsum + mk(T.x * el.x, T.y * el.y, T.z * el.z);
+                        }
+                        nc->pb = dot(h.n, nd) / (sqrt(dot(nd, nd)) * (R)3.141592653589793);
                     }
                 }
                 T = mk(T.x * att.x, T.y * att.y, T.z * att.z);
@@ -382,7 +472,9 @@ RT_HD PixelResult trace_pixel_lit(const SceneView<R>& sc, const ImageParams& im,
     static_assert((feat_of<ACC>() & F_LIGHT) != 0, "a lit mode");
     V3<R> dir[RT_REC_DEPTH];                   // rec: the bounces' direct terms
     // dsum: the segment's (rec) or the sample's (forward) direct light
-    LightCtx<R> lc{mk<R>(0, 0, 0), &res.work, stk};
+    constexpr bool NEE = (feat_of<ACC>() & F_NEE) != 0;     // emitter sampling: pb = 0 at every sample start
+    LightState<R, true, NEE> lc{mk<R>(0, 0, 0), &res.work, stk};
+    if constexpr (NEE) lc.max_depth = im.max_depth;
     int nb = 0;
     bool skip_tri = false;                     // tri_exit_bound (pt_core.h)
     if (s < s_end) start_sample(sc, im, i, j, pkey, s, g, o, d);
@@ -421,6 +513,7 @@ RT_HD PixelResult trace_pixel_lit(const SceneView<R>& sc, const ImageParams& im,
             ++s;
             T = mk<R>(1, 1, 1);
             depth = im.max_depth;
+            if constexpr (NEE) lc.pb = (R)0;
             if (s < s_end) start_sample(sc, im, i, j, pkey, s, g, o, d);
         }
         if (RT_PROFILE) res.cyc[2] += RT_TICK() - t2;

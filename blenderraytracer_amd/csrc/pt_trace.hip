@@ -306,8 +306,10 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
     Rng<R> g;
     V3<R> o, d, T;
     constexpr bool LIT = (feat_of<ACC>() & F_LIGHT) != 0;
-    LightState<R, LIT> lc{mk<R>(0, 0, 0), &res.work, stk};   // LIT: dsum = the sample's direct light so far, sum of T (.) direct;
+    constexpr bool NEE = (feat_of<ACC>() & F_NEE) != 0;   // emitter sampling: the scatter density lc.pb, 0 at a sample's start
+    LightState<R, LIT, NEE> lc{mk<R>(0, 0, 0), &res.work, stk};   // LIT: dsum = the sample's direct light so far, sum of T (.) direct;
                                                       // the shadow rays walk with the lane's own (idle) stack
+    if constexpr (NEE) lc.max_depth = im.max_depth;
     auto begin_item = [&](const uint32_t k) {
         uint32_t sr;
         if (nv == 64) { m = k & 63; sr = k >> 6; }
@@ -323,6 +325,7 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
         depth = im.max_depth;
         isegs = 0;
         if constexpr (LIT) lc.dsum = mk<R>(0, 0, 0);
+        if constexpr (NEE) lc.pb = (R)0;
         start_sample<R, false, feat_of<ACC>()>(sc, im, i, j, pkey, s, g, o, d);
     };
     uint32_t next = 64;                       // items [0, 64) are dealt to lanes 0..63 up front
@@ -795,6 +798,11 @@ RT_ONEWAVE_INST(double, ACC_BRUTE_LIT)
 RT_ONEWAVE_INST(double, ACC_BVH_STACK_LIT)
 RT_ONEWAVE_INST(float, ACC_BRUTE_LIT)
 RT_ONEWAVE_INST(float, ACC_BVH_STACK_LIT)
+// renders that sample the scene's emitters (MIS): the same two walks, textures and scene lights included
+RT_ONEWAVE_INST(double, ACC_BRUTE_NEE)
+RT_ONEWAVE_INST(double, ACC_BVH_STACK_NEE)
+RT_ONEWAVE_INST(float, ACC_BRUTE_NEE)
+RT_ONEWAVE_INST(float, ACC_BVH_STACK_NEE)
 #undef RT_ONEWAVE_INST
 #else   // !RT_ONEWAVE_TU: the rest of the file
 
@@ -1349,6 +1357,43 @@ template hipError_t launch_occluded<double>(const SceneView<double>&, bool, cons
                                             hipStream_t);
 template hipError_t launch_occluded<float>(const SceneView<float>&, bool, const double*, const double*, size_t, uint8_t*,
                                            hipStream_t);
+
+// ---- the emitter-sampling kernels' sample at given points (rt_emitter_samples: emitter_query) ----
+template <class R, int ACC>
+__global__ __launch_bounds__(64) void emitter_samples_kernel(const SceneView<R> sc, const double* __restrict__ pts,
+                                                             const uint32_t* __restrict__ keys, const size_t n,
+                                                             double* __restrict__ out, int* __restrict__ ev) {
+    __shared__ int stack[RT_BVH_STACK * 64];
+    const BvhStack stk{stack + threadIdx.x, 64};
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n) return;
+    const double* q = pts + 6 * r;
+    const V3<R> x = mk<R>((R)q[0], (R)q[1], (R)q[2]), nn = mk<R>((R)q[3], (R)q[4], (R)q[5]);
+    Work w{0, 0, 0, 0, 0, 0};
+    const EmitterQuery<R> s = emitter_query<R, ACC>(sc, x, nn, keys[r], w, stk);
+    out[5 * r] = (double)s.om.x;
+    out[5 * r + 1] = (double)s.om.y;
+    out[5 * r + 2] = (double)s.om.z;
+    out[5 * r + 3] = (double)s.p_l;
+    out[5 * r + 4] = (double)s.t_e;
+    ev[2 * r] = s.e;
+    ev[2 * r + 1] = s.visible ? 1 : 0;
+}
+
+template <class R>
+hipError_t launch_emitter_samples(const SceneView<R>& sc, bool bvh, const double* points, const uint32_t* keys, size_t n,
+                                  double* out, int* ev, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (sc.num_emitters <= 0) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (bvh) hipLaunchKernelGGL((emitter_samples_kernel<R, ACC_BVH_STACK_NEE>), grid, dim3(64), 0, stream, sc, points, keys, n, out, ev);
+    else hipLaunchKernelGGL((emitter_samples_kernel<R, ACC_BRUTE_NEE>), grid, dim3(64), 0, stream, sc, points, keys, n, out, ev);
+    return hipGetLastError();
+}
+template hipError_t launch_emitter_samples<double>(const SceneView<double>&, bool, const double*, const uint32_t*, size_t,
+                                                   double*, int*, hipStream_t);
+template hipError_t launch_emitter_samples<float>(const SceneView<float>&, bool, const double*, const uint32_t*, size_t,
+                                                  double*, int*, hipStream_t);
 
 // ---- Texture.value at given points (rt_texture_values: texture_value, the trace kernels' function) ----
 template <class R>

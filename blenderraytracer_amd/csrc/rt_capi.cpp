@@ -112,6 +112,9 @@ struct DeviceScene {
     DevBuf<TexRec<R>> tex_recs;
     DevBuf<int> tex_perms, mat_tex;
     DevBuf<LightRec<R>> light_recs;      // scene lights (lit scenes only): the LightView follows the TexView
+    DevBuf<EmitterRec<R>> emitter_recs;  // emitter sampling: the EmitterView follows the LightView
+    DevBuf<int> sphere_listed;
+    DevBuf<R> tri_area;
     SceneView<R> view{};
     void release() {
         runs.release(); spheres.release(); sphere_filter.release(); sphere_r.release(); sphere_inv_r.release(); planes.release(); boxes.release(); tris.release();
@@ -120,6 +123,7 @@ struct DeviceScene {
         bvh_tri_leaf.release(); tri_filter.release(); tri_exit.release(); big_sphere_leaf.release();
         sphere_wide.release(); tri_wide.release(); grid_cell.release(); grid_leaf.release();
         tex_recs.release(); tex_perms.release(); mat_tex.release(); light_recs.release();
+        emitter_recs.release(); sphere_listed.release(); tri_area.release();
     }
 };
 
@@ -132,8 +136,8 @@ int build_device(DeviceScene<R>& ds, const HostScene& hs, const rt_scene_desc& d
     UP(runs, hs.runs); UP(spheres, rec.spheres); UP(sphere_filter, rec.sphere_filter); UP(sphere_r, rec.sphere_r); UP(sphere_inv_r, rec.sphere_inv_r); UP(planes, rec.planes);
     UP(boxes, rec.boxes); UP(tris, rec.tris); UP(sphere_mat, hs.sphere_mat); UP(plane_mat, hs.plane_mat);
     UP(box_mat, hs.box_mat); UP(tri_mat, hs.tri_mat); UP(mats, rec.mats);
-    const bool textured = !rec.tex_recs.empty(), lit = !rec.light_recs.empty();
-    if (textured || lit) {   // the TexView over the uploaded arrays goes behind the world's table (tex_view)
+    const bool textured = !rec.tex_recs.empty(), lit = !rec.light_recs.empty(), nee = !rec.emitter_recs.empty();
+    if (textured || lit || nee) {   // the TexView over the uploaded arrays goes behind the world's table (tex_view)
         UP(tex_recs, rec.tex_recs); UP(tex_perms, rec.tex_perms); UP(mat_tex, rec.mat_tex);
         rec.set_tex_view(TexView<R>{ds.tex_recs.p, ds.tex_perms.p, ds.mat_tex.p, (int)rec.tex_recs.size(),
                                     (int)(rec.tex_perms.size() / 512)});
@@ -141,6 +145,11 @@ int build_device(DeviceScene<R>& ds, const HostScene& hs, const rt_scene_desc& d
     if (lit) {               // ... and the LightView behind it (light_view)
         UP(light_recs, rec.light_recs);
         rec.set_light_view(LightView<R>{ds.light_recs.p, (int)rec.light_recs.size(), 0});
+    }
+    if (nee) {               // ... and the EmitterView behind that (emitter_view)
+        UP(emitter_recs, rec.emitter_recs); UP(sphere_listed, rec.sphere_listed); UP(tri_area, rec.tri_area);
+        rec.set_emitter_view(EmitterView<R>{ds.emitter_recs.p, ds.sphere_listed.p, ds.tri_area.p,
+                                            (int)rec.emitter_recs.size(), 0});
     }
     UP(perm, rec.perm);
     UP(plane_obj, hs.plane_obj); UP(box_obj, hs.box_obj); UP(sphere_nodes, hs.sphere_bvh); UP(tri_nodes, hs.tri_bvh);
@@ -398,6 +407,7 @@ struct rt_scene {
     // buffers.  g_mean: sum / samples; guides: aov_kernel's records; g_ping / g_pong: the levels' frames
     // (rt_guided_filter_device uses g_ping beside the caller's d_out).  g_used is recorded after every use of
     // these buffers and waited for before the next, on whichever streams
+    bool emitter_sampling = false;  // rt_scene_set_emitter_sampling (the list itself: hs.emit_kind / emit_idx)
     bool guided_on = false;
     rt_guided_params guided{};
     DevBuf<double> g_mean, g_ping, g_pong;
@@ -1946,6 +1956,87 @@ int rt_scene_set_guided(rt_scene* sc, const rt_guided_params* p) {
     if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
     sc->guided_on = p != nullptr;
     if (p) sc->guided = *p;
+    return RT_OK;
+}
+
+int rt_scene_set_emitter_sampling(rt_scene* sc, int32_t on) {
+    if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
+    const bool was = sc->emitter_sampling;
+    const std::vector<int> kind0 = sc->hs.emit_kind, idx0 = sc->hs.emit_idx;
+    std::string err;
+    if (!build_emitters(sc->hs, sc->desc.d, on != 0, err)) {
+        sc->emitter_sampling = false;
+        if (!kind0.empty()) (void)rt_scene_set_emitter_sampling(sc, 0);     // off: the plain records again
+        return fail(RT_ERR_INVALID, "%s", err.c_str());
+    }
+    sc->emitter_sampling = on != 0;
+    if (was == sc->emitter_sampling && kind0 == sc->hs.emit_kind && idx0 == sc->hs.emit_idx) return RT_OK;
+    if (kind0.empty() && sc->hs.emit_idx.empty()) return RT_OK;             // no emitter either way: nothing moves
+    // the records of every device that holds the scene, with or without the emitter list (the arrays in place:
+    // DevBuf::ensure keeps a buffer that is large enough); what the sums on the device were is no longer what a
+    // render would add to
+    std::vector<DeviceState*> all{&sc->home};
+    for (DeviceState* r : sc->replicas)
+        if (r) all.push_back(r);
+    for (DeviceState* ds : all) {
+        ds->sync_all();
+        HIP_TRY(hipSetDevice(ds->device));
+        int rc;
+        if ((rc = build_device(ds->s64, sc->hs, sc->desc.d)) || (rc = build_device(ds->s32, sc->hs, sc->desc.d))) return rc;
+    }
+    sc->ckpt_pixels = 0;
+    sc->ckpt_done = 0;
+    return RT_OK;
+}
+
+int rt_scene_emitter_count(rt_scene* sc, int32_t* count) {
+    if (!sc || !count) return fail(RT_ERR_INVALID, "NULL argument");
+    *count = (int32_t)sc->hs.emit_idx.size();
+    return RT_OK;
+}
+
+int rt_emitter_samples(rt_scene* sc, int32_t precision, int32_t accel, const double* points, const uint32_t* keys,
+                       size_t n, int32_t* emitter, double* omega, double* p_l, double* t_e, uint8_t* visible) {
+    if (!sc || (n > 0 && (!points || !keys))) return fail(RT_ERR_INVALID, "NULL argument");
+    if (precision != RT_PREC_F64 && precision != RT_PREC_F32) return fail(RT_ERR_INVALID, "precision %d", precision);
+    rt_settings s{};
+    s.accel = accel;
+    if (s.accel < RT_ACCEL_AUTO || s.accel > RT_ACCEL_BVH) return fail(RT_ERR_INVALID, "accel %d", accel);
+    if (sc->hs.emit_idx.empty()) return fail(RT_ERR_INVALID, "emitter sampling is off, or the scene lists no emitter");
+    int rc = check_accel(sc, &s);
+    if (rc) return rc;
+    if (n == 0) return RT_OK;
+    DeviceState& ds = sc->home;
+    HIP_TRY(hipSetDevice(ds.device));
+    DevBuf<double> d_pts, d_out;      // d_out: n x 5 doubles (omega, p_l, t_e)
+    DevBuf<uint32_t> d_keys;
+    DevBuf<int> d_ev;                 // n x 2 ints: emitter, visible
+    hipError_t e = d_pts.ensure(6 * n);
+    if (e == hipSuccess) e = d_keys.ensure(n);
+    if (e == hipSuccess) e = d_out.ensure(5 * n);
+    if (e == hipSuccess) e = d_ev.ensure(2 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pts.p, points, 6 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_keys.p, keys, n * sizeof(uint32_t), hipMemcpyHostToDevice, ds.stream);
+    const bool bvh = use_bvh(sc, &s);
+    if (e == hipSuccess)
+        e = with_view(ds, precision, [&](const auto& v) {
+            return launch_emitter_samples(v, bvh, d_pts.p, d_keys.p, n, d_out.p, d_ev.p, ds.stream);
+        });
+    std::vector<double> out(5 * n);
+    std::vector<int> ev(2 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), d_out.p, 5 * n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ev.data(), d_ev.p, 2 * n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_pts.release(); d_keys.release(); d_out.release(); d_ev.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_emitter_samples: %s", hipGetErrorString(e));
+    for (size_t i = 0; i < n; ++i) {
+        if (omega) for (int k = 0; k < 3; ++k) omega[3 * i + k] = out[5 * i + k];
+        if (p_l) p_l[i] = out[5 * i + 3];
+        if (t_e) t_e[i] = out[5 * i + 4];
+        if (emitter) emitter[i] = ev[2 * i];
+        if (visible) visible[i] = (uint8_t)ev[2 * i + 1];
+    }
     return RT_OK;
 }
 

@@ -4,13 +4,14 @@
 //                 [--aa supersampling|stochastic|none] [--tone reinhard|aces|linear]
 //                 [--exposure E] [--gamma G] [--denoise STRENGTH] [--precision f64|f32]
 //                 [--accel auto|bvh|brute] [--frames K] [--warmup W] [--batch B] [--device N]
-//                 [--out image.ppm|image.pam] [--lights]
+//                 [--out image.ppm|image.pam] [--lights] [--nee]
 //                 [--guided] [--guided-levels N] [--guided-sigma C,A,N,Z] [--aovs PREFIX]
 //
 // --guided: the edge-aware guided filter over the linear mean (rt_scene_set_guided; --guided-levels and
 // --guided-sigma colour,albedo,normal,depth override the defaults and imply it)
 // --aovs PREFIX: the feature buffers of the primary hit (rt_aovs) as PREFIX.albedo.pfm, PREFIX.normal.pfm (colour
 // PFM) and PREFIX.depth.pfm (greyscale PFM), little-endian binary32, rows bottom-up as PFM has them
+// --nee: sample the scene's emissive spheres and triangles with MIS (rt_scene_set_emitter_sampling; off by default)
 // --lights: direct lighting from the scene's "lights" (rt_json_scene_desc_lit; off by default)
 //
 // Does what a reference user does in the browser: RayTracer(width, height) -> loadFromJSON(scene)
@@ -74,7 +75,7 @@ int main(int argc, char** argv) {
     if (argc < 2 || !strcmp(argv[1], "--help")) {
         fprintf(stderr, "usage: rt_render_cli scene.json [--width W --height H --spp S --depth D --seed N --aa MODE "
                         "--tone MAP --exposure E --gamma G --denoise STRENGTH --precision f64|f32 --accel auto|bvh|brute "
-                        "--frames K --warmup W --batch B --device N --out FILE --lights --guided --guided-levels N "
+                        "--frames K --warmup W --batch B --device N --out FILE --lights --nee --guided --guided-levels N "
                         "--guided-sigma C,A,N,Z --aovs PREFIX]\n");
         return argc < 2 ? 2 : 0;
     }
@@ -83,12 +84,13 @@ int main(int argc, char** argv) {
     double spp = 4, depth = 5, exposure = 1.0, gamma = 2.2, denoise = 0;
     uint32_t seed = 1;
     std::string aa = "supersampling", tone = "reinhard", precision = "f64", accel = "auto", out, aovs;
-    bool lights = false, guided = false;
+    bool lights = false, guided = false, nee = false;
     rt_guided_params gp{RT_GUIDED_DEFAULT_LEVELS, 0, RT_GUIDED_DEFAULT_SIGMA_COLOR, RT_GUIDED_DEFAULT_SIGMA_ALBEDO,
                         RT_GUIDED_DEFAULT_SIGMA_NORMAL, RT_GUIDED_DEFAULT_SIGMA_DEPTH};
     for (int i = 2; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--lights") { lights = true; continue; }
+        if (a == "--nee") { nee = true; continue; }
         if (a == "--guided") { guided = true; continue; }
         if (i + 1 >= argc) die("missing value for ", a.c_str());
         const char* v = argv[++i];
@@ -130,6 +132,7 @@ int main(int argc, char** argv) {
     if (!desc) die("--lights: ", rt_last_error());
     check(rt_scene_create(desc, device, &scene), "uploading the scene");
     const double upload_ms = now_ms() - t_up;
+    if (nee) check(rt_scene_set_emitter_sampling(scene, 1), "--nee");
     if (guided) check(rt_scene_set_guided(scene, &gp), "--guided");
 
     rt_settings s{};

@@ -38,6 +38,9 @@ struct HostScene {   // precision-independent staging, binary64 as packed by the
     // build_tri_exit (pt_core.h tri_exit_bound): {C+, C-} per triangle and the bound's constants
     std::vector<double> tri_exit;
     double exit_k0 = 0, exit_k1 = 0, exit_k2 = 0, exit_l1 = -1, exit_l2 = -1;
+    // build_emitters (emitter sampling switched on): the listed emitters in World.objects order, mesh triangles
+    // in triangle-array order — kind (pt_core.h EmitterKind) and index into spheres / tris; empty: off, or none
+    std::vector<int> emit_kind, emit_idx;
 };
 
 inline bool pack_host(const rt_scene_desc& d, HostScene& hs, std::string& err) {
@@ -119,6 +122,62 @@ inline bool pack_host(const rt_scene_desc& d, HostScene& hs, std::string& err) {
             err = buf;
             return false;
         }
+    }
+    return true;
+}
+
+// The emitter list of a scene whose emitters are to be sampled (rt_scene_set_emitter_sampling): every sphere
+// whose material is Emissive with finite r2 > 0 and a finite emission with a component > 0, and every triangle
+// (standalone or of a mesh) with such a material, a finite stored normal and finite area |e1 x e2| / 2 > 0.
+// Boxes and planes are not listed: their emission keeps weight 1.  on = false empties the list.  false: more
+// than RT_MAX_EMITTERS (the list is left empty).
+inline double tri_area64(const double* t) {                       // t: v0, e1, e2, n (HostScene::tris)
+    const double cx = t[4] * t[8] - t[5] * t[7], cy = t[5] * t[6] - t[3] * t[8], cz = t[3] * t[7] - t[4] * t[6];
+    return std::sqrt(cx * cx + cy * cy + cz * cz) / 2.0;
+}
+inline bool build_emitters(HostScene& hs, const rt_scene_desc& d, bool on, std::string& err) {
+    hs.emit_kind.clear();
+    hs.emit_idx.clear();
+    if (!on) return true;
+    auto emits = [&](int mat) {
+        const rt_material_desc& m = d.materials[mat];
+        if (m.type != RT_MAT_EMISSIVE) return false;
+        bool finite = true, some = false;
+        for (int k = 0; k < 3; ++k) {
+            finite = finite && std::isfinite(m.emission[k]);
+            some = some || m.emission[k] > 0.0;
+        }
+        return finite && some;
+    };
+    size_t si = 0, ti = 0;
+    const size_t ns = hs.sphere_mat.size(), nt = hs.tri_mat.size();
+    while (si < ns || ti < nt) {
+        // the two arrays are in World.objects order each: merge them by object index
+        if (ti >= nt || (si < ns && hs.sphere_obj[si] < hs.tri_obj[ti])) {
+            const double r2 = hs.spheres[4 * si + 3];
+            if (emits(hs.sphere_mat[si]) && std::isfinite(r2) && r2 > 0.0) {
+                hs.emit_kind.push_back(EMIT_SPHERE);
+                hs.emit_idx.push_back((int)si);
+            }
+            ++si;
+        } else {
+            const double* t = &hs.tris[12 * ti];
+            const double a = tri_area64(t);
+            if (emits(hs.tri_mat[ti]) && std::isfinite(t[9]) && std::isfinite(t[10]) && std::isfinite(t[11]) &&
+                std::isfinite(a) && a > 0.0) {
+                hs.emit_kind.push_back(EMIT_TRI);
+                hs.emit_idx.push_back((int)ti);
+            }
+            ++ti;
+        }
+    }
+    if (hs.emit_idx.size() > (size_t)RT_MAX_EMITTERS) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "%zu emitters (at most %d)", hs.emit_idx.size(), RT_MAX_EMITTERS);
+        err = buf;
+        hs.emit_kind.clear();
+        hs.emit_idx.clear();
+        return false;
     }
     return true;
 }
@@ -734,6 +793,16 @@ struct HostRecords {
         perm.resize(std::max(perm.size(), kLightViewAt + sizeof(LightView<R>) / sizeof(int)));
         memcpy(perm.data() + kLightViewAt, &lv, sizeof lv);
     }
+    // emitter sampling (empty unless HostScene::emit_idx lists emitters): such a scene has mat_tex and a TexView
+    // as a lit one has, a LightView (zeros without lights) and its EmitterView behind that (emitter_view)
+    std::vector<EmitterRec<R>> emitter_recs;
+    std::vector<int> sphere_listed;
+    std::vector<R> tri_area;
+    void set_emitter_view(const EmitterView<R>& ev) {
+        static_assert(sizeof(EmitterView<R>) % sizeof(int) == 0, "EmitterView in ints");
+        perm.resize(std::max(perm.size(), kEmitterViewAt + sizeof(EmitterView<R>) / sizeof(int)));
+        memcpy(perm.data() + kEmitterViewAt, &ev, sizeof ev);
+    }
     // BVH leaf-order records (bvh_sphere_leaf[k] describes spheres[bvh_sphere_leaf[k].id], same for
     // triangles)
     std::vector<SphereLeaf<R>> bvh_sphere_leaf;
@@ -826,6 +895,32 @@ void make_records(const HostScene& hs, const rt_scene_desc& d, HostRecords<R>& o
             out.light_recs[i] = r;
         }
     }
+    if (!hs.emit_idx.empty()) {
+        if (out.mat_tex.empty()) out.mat_tex.assign((size_t)std::max(1, d.num_materials), -1);
+        out.sphere_listed.assign(std::max<size_t>(1, out.spheres.size()), 0);
+        out.tri_area.assign(std::max<size_t>(1, out.tris.size()), (R)0);
+        out.emitter_recs.resize(hs.emit_idx.size());
+        for (size_t e = 0; e < hs.emit_idx.size(); ++e) {
+            EmitterRec<R> r{};
+            r.kind = hs.emit_kind[e];
+            r.idx = hs.emit_idx[e];
+            int mat;
+            if (r.kind == EMIT_SPHERE) {
+                const SphereRec<R>& s = out.spheres[r.idx];
+                r.g[0] = s.cx; r.g[1] = s.cy; r.g[2] = s.cz; r.g[3] = s.r2;
+                out.sphere_listed[r.idx] = 1;
+                mat = hs.sphere_mat[r.idx];
+            } else {
+                const double* t = &hs.tris[12 * (size_t)r.idx];
+                for (int k = 0; k < 12; ++k) r.g[k] = (R)t[k];
+                r.area = (R)tri_area64(t);
+                out.tri_area[r.idx] = r.area;
+                mat = hs.tri_mat[r.idx];
+            }
+            for (int k = 0; k < 3; ++k) r.le[k] = out.mats[mat].c[k];
+            out.emitter_recs[e] = r;
+        }
+    }
     auto leaf = [&](int id) {
         SphereLeaf<R> L{};
         if constexpr (sizeof(R) == 8) L.f = out.sphere_filter[id];
@@ -856,6 +951,7 @@ void fill_view_constants(SceneView<R>& v, const HostScene& hs, const rt_scene_de
     v.num_mats = d.num_materials;
     v.num_tex = scene_textured(d) ? d.num_textures : 0;
     v.num_lights = d.num_lights;
+    v.num_emitters = (int)hs.emit_idx.size();
     v.num_boxes = (int)hs.box_mat.size();
     v.num_sphere_nodes = (int)hs.sphere_bvh.size();
     v.num_tri_nodes = (int)hs.tri_bvh.size();
@@ -924,10 +1020,13 @@ inline SceneView<double> host_view(const HostScene& hs, const rt_scene_desc& d, 
     v.big_spheres = rec.big_sphere_leaf.data();
     v.sphere_wide = hs.sphere_wide.data(); v.tri_wide = hs.tri_wide.data();
     v.grid_cell = hs.grid_cell.data(); v.grid_leaf = rec.grid_leaf.data();
-    if (!rec.tex_recs.empty() || !rec.light_recs.empty()) {
+    if (!rec.tex_recs.empty() || !rec.light_recs.empty() || !rec.emitter_recs.empty()) {
         rec.set_tex_view(TexView<double>{rec.tex_recs.data(), rec.tex_perms.data(), rec.mat_tex.data(),
                                          (int)rec.tex_recs.size(), (int)(rec.tex_perms.size() / 512)});
         if (!rec.light_recs.empty()) rec.set_light_view(LightView<double>{rec.light_recs.data(), (int)rec.light_recs.size(), 0});
+        if (!rec.emitter_recs.empty())
+            rec.set_emitter_view(EmitterView<double>{rec.emitter_recs.data(), rec.sphere_listed.data(), rec.tri_area.data(),
+                                                     (int)rec.emitter_recs.size(), 0});
         v.perm = rec.perm.data();
     }
     fill_view_constants(v, hs, d);

@@ -88,7 +88,8 @@ function guidedOf(rt, opts) {
 export function gpuAovs(rt, opts = {}) {
     const nat = loadNative();
     const lit = rt.directLighting !== undefined ? !!rt.directLighting : !!opts.directLighting;
-    const scene = residentScene(rt, nat, opts.device || 0, lit);
+    const nee = rt.emitterSampling !== undefined ? !!rt.emitterSampling : !!opts.emitterSampling;
+    const scene = residentScene(rt, nat, opts.device || 0, lit, nee);
     return nat.aovs(scene, {
         width: rt.width, height: rt.height, precision: PRECISION[opts.precision || 'f64'], accel: ACCEL[opts.accel || 'auto'],
         cropX0: opts.crop ? opts.crop[0] : 0, cropY0: opts.crop ? opts.crop[1] : 0,
@@ -124,14 +125,15 @@ function samePacked(a, b) {
 // The scene resident on the GPU for this RayTracer: packed from world / camera at every render (cheap)
 // and compared byte for byte with the cached one, so the upload and the BVH build happen only when
 // the scene or the camera changed (presets, loadFromJSON, updateCamera, updateBackground...).
-function residentScene(rt, nat, device, lights) {
+function residentScene(rt, nat, device, lights, emitters = false) {
     const packed = packScene(rt.world, rt.camera, lights ? { lights: true } : {});
     const c = rt.__gpuScene;
-    if (c && c.device === device && samePacked(c.packed, packed)) return c.scene;
+    if (c && c.device === device && c.emitters === emitters && samePacked(c.packed, packed)) return c.scene;
     if (c) nat.destroyScene(c.scene);
     rt.__gpuScene = null;
-    const scene = nat.createScene(packed, device);
-    Object.defineProperty(rt, '__gpuScene', { value: { scene, packed, device }, writable: true, configurable: true, enumerable: false });
+    // emitters: the scene's emissive spheres and triangles are sampled (rt_scene_set_emitter_sampling)
+    const scene = nat.createScene(packed, device, emitters ? 1 : 0);
+    Object.defineProperty(rt, '__gpuScene', { value: { scene, packed, device, emitters }, writable: true, configurable: true, enumerable: false });
     return scene;
 }
 
@@ -168,7 +170,8 @@ export async function gpuRender(rt, onProgress, opts = {}) {
     // direct lighting (opt-in): the RayTracer's own directLighting member (GpuRayTracer), else the option
     // (installGpuRender on a reference RayTracer, which has no such member)
     const lit = rt.directLighting !== undefined ? !!rt.directLighting : !!opts.directLighting;
-    const scene = residentScene(rt, nat, opts.device || 0, lit);
+    const nee = rt.emitterSampling !== undefined ? !!rt.emitterSampling : !!opts.emitterSampling;
+    const scene = residentScene(rt, nat, opts.device || 0, lit, nee);
     // a resident checkpoint is resumed from the device (decided before this render supersedes it)
     const resume = opts.resume && opts.resume.resident ? { resident: true, samplesDone: opts.resume.samplesDone }
         : opts.resume ? { sums: opts.resume.sums, samplesDone: opts.resume.samplesDone } : undefined;
@@ -237,6 +240,7 @@ export class GpuRayTracer {
         this.denoising = false; this.denoiseStrength = 0.5;
         this.directLighting = !!opts.directLighting;                // opt-in: render world.lights
         this.guidedDenoise = !!opts.guidedDenoise;                  // opt-in: the guided filter (INTEGRATION.md)
+        this.emitterSampling = !!opts.emitterSampling;              // opt-in: sample emissive geometry with MIS (INTEGRATION.md §10)
         const d = defaultScene(this.width, this.height, permutation(opts.seed || 0));
         this.world = d.world;
         this.camera = d.camera;
@@ -272,6 +276,7 @@ export class GpuRayTracer {
         this.denoising = p.denoising || false;
         this.denoiseStrength = p.denoiseStrength || 0.5;
         if (p.directLighting !== undefined) this.directLighting = !!p.directLighting;   // (not a reference setting)
+        if (p.emitterSampling !== undefined) this.emitterSampling = !!p.emitterSampling;   // (nor this)
         // the guided filter's keys, read only when present (not reference settings either)
         if (p.guidedDenoise !== undefined) this.guidedDenoise = !!p.guidedDenoise;
         for (const k of ['guidedLevels', 'guidedSigmaColor', 'guidedSigmaAlbedo', 'guidedSigmaNormal', 'guidedSigmaDepth'])

@@ -59,9 +59,10 @@ GUIDED_SIGMAS = dict(capi.RT_GUIDED_DEFAULT_SIGMAS)
 
 class GpuRayTracer:
     def __init__(self, width, height, seed=0, device=0, precision=capi.RT_PREC_F64, accel=capi.RT_ACCEL_AUTO,
-                 sum_order=capi.RT_SUM_POOL, direct_lighting=False):
+                 sum_order=capi.RT_SUM_POOL, direct_lighting=False, emitter_sampling=False):
         self.width, self.height = int(width), int(height)
         self.direct_lighting = bool(direct_lighting)   # opt-in: render World.lights
+        self.emitter_sampling = bool(emitter_sampling)  # opt-in: sample emissive geometry with MIS
         self.seed = seed
         self.device = device
         self.precision = precision
@@ -117,6 +118,9 @@ class GpuRayTracer:
         if "directLighting" in params and bool(truthy(g("directLighting"))) != self.direct_lighting:
             self.direct_lighting = not self.direct_lighting
             self._dirty = True                      # the lights are part of the scene on the device
+        if "emitterSampling" in params and bool(truthy(g("emitterSampling"))) != self.emitter_sampling:
+            self.emitter_sampling = not self.emitter_sampling
+            self._dirty = True                      # ... and so is the emitter list
         # the guided filter's keys, read only when present: a dict without them leaves the filter as it was
         if "guidedDenoise" in params:
             self.guided_denoise = bool(truthy(g("guidedDenoise")))
@@ -154,8 +158,34 @@ class GpuRayTracer:
             h = C.c_void_p()
             capi.check(lib.rt_scene_create(C.byref(self.packed().desc), self.device, C.byref(h)))
             self._scene = h
+            if self.emitter_sampling:
+                capi.check(lib.rt_scene_set_emitter_sampling(h, 1))
             self._dirty = False
         return self._scene
+
+    def emitter_count(self):
+        """Listed emitters of the scene on the device (rt_scene_emitter_count; 0 while emitter sampling is off)."""
+        n = C.c_int32()
+        capi.check(capi.load_library().rt_scene_emitter_count(self.scene_handle(), C.byref(n)))
+        return n.value
+
+    def emitter_samples(self, points, keys):
+        """rt_emitter_samples: the emitter-sampling kernels' own sample at points (n x 6: hit point, facing normal)
+        with the emitter streams' keys (n) -> dict of emitter (n), omega (n, 3), p_l, t_e (n), visible (n, bool)."""
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 6)
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        n = len(points)
+        assert keys.shape == (n,)
+        res = {"emitter": np.zeros(n, dtype=np.int32), "omega": np.zeros((n, 3)), "p_l": np.zeros(n), "t_e": np.zeros(n),
+               "visible": np.zeros(n, dtype=np.uint8)}
+        dp = C.POINTER(C.c_double)
+        capi.check(capi.load_library().rt_emitter_samples(
+            self.scene_handle(), self.precision, self.accel, points.ctypes.data_as(dp),
+            keys.ctypes.data_as(C.POINTER(C.c_uint32)), n, res["emitter"].ctypes.data_as(C.POINTER(C.c_int32)),
+            res["omega"].ctypes.data_as(dp), res["p_l"].ctypes.data_as(dp), res["t_e"].ctypes.data_as(dp),
+            res["visible"].ctypes.data_as(C.POINTER(C.c_uint8))))
+        res["visible"] = res["visible"].astype(bool)
+        return res
 
     def guided_params(self):
         """rt_guided_params of the current settings (None: the filter is off)."""

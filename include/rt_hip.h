@@ -395,8 +395,8 @@ int rt_texture_values(rt_scene* scene, int32_t precision, int32_t texture, const
 
 /* Diagnostic: the walk a render with these precision / accel settings runs on this scene — 0 World.objects
  * order (brute force), 1 a BVH tree walk, 2 the uniform grid over the spheres (sphere-only scenes where
- * the host's sampled cost estimate prefers it, scene_pack.h choose_walk; never for a scene with textures
- * or lights, whose kernels walk World order or the trees); < 0 an error status.  Every walk finds the same closest
+ * the host's sampled cost estimate prefers it, scene_pack.h choose_walk; never for a scene with textures,
+ * lights or sampled emitters, whose kernels walk World order or the trees); < 0 an error status.  Every walk finds the same closest
  * hit; they differ in speed only. */
 int rt_scene_walk(rt_scene* scene, int32_t precision, int32_t accel);
 
@@ -448,6 +448,31 @@ int rt_guided_filter_device(rt_scene* scene, int32_t width, int32_t height, cons
  * preview frames are not filtered, and the scene's sums are never overwritten: checkpoints and resumes are
  * unchanged.  The parameters are validated before any device is touched (RT_ERR_INVALID). */
 int rt_scene_set_guided(rt_scene* scene, const rt_guided_params* params);
+
+/* Emitter sampling (next-event estimation with multiple importance sampling): an append-only
+ * extension of generation 3.  Off by default.  While on, every Lambertian / TexturedLambertian hit but the last
+ * allowed bounce's samples one of the scene's listed emitters — every Emissive sphere (finite r2 > 0) and
+ * triangle (standalone or of a mesh; finite normal and area > 0) whose emission is finite with a component
+ * > 0, in World.objects order — and the emission a scattered ray meets is weighted by the balance heuristic,
+ * so the render has the plain render's expectation with less variance.  Emissive boxes and planes are not
+ * listed and keep weight 1.  A scene without listed emitters renders exactly what it rendered before.
+ * Switching it changes what later renders compute: not to be called while a render of the scene is in flight,
+ * and a checkpoint taken before does not resume after.  RT_ERR_INVALID: scene NULL, or more than
+ * RT_MAX_EMITTERS listed (the setting is then left off). */
+#define RT_MAX_EMITTERS 1048576
+int rt_scene_set_emitter_sampling(rt_scene* scene, int32_t on);
+/* The number of listed emitters (0 while emitter sampling is off). */
+int rt_scene_emitter_count(rt_scene* scene, int32_t* count);
+/* Diagnostic (tests): the emitter-sampling kernels' own sample for `n` queries on the scene's device, the twin of
+ * rt_occluded.  points: host, n x 6 doubles (hit point x, facing normal n; rounded to binary32 first in
+ * RT_PREC_F32); keys: n 32-bit keys of the emitter stream (the kernels derive theirs from the sample's key and
+ * the bounce).  Outputs (host, n each, any may be NULL): emitter (index in the list), omega (n x 3, the unit
+ * direction), p_l (its solid-angle density, the 1 / N of the emitter choice included), t_e (the sampled
+ * primitive's own candidate t along omega), visible (1: nothing nearer than t_e).  Stages a query does not reach
+ * leave zeros: no sample (inside the sphere, an edge-on triangle) omega = p_l = 0; n . omega <= 0 or no candidate
+ * t_e = 0 and visible = 0.  RT_ERR_INVALID unless emitter sampling is on with at least one emitter. */
+int rt_emitter_samples(rt_scene* scene, int32_t precision, int32_t accel, const double* points, const uint32_t* keys,
+                       size_t n, int32_t* emitter, double* omega, double* p_l, double* t_e, uint8_t* visible);
 
 /* Request cancellation of an in-flight rt_render on `scene` (the pool kernels read it between items;
  * see rt_render). */
