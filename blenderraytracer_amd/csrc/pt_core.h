@@ -215,7 +215,8 @@ template <class R> struct MatRec { int type, pad; R c[3]; R p; };
 // BVH leaf records in leaf order: everything one primitive test and its acceptance need (the
 // binary32 filter, the R-precision geometry, World index, World.objects index, material) in one
 // contiguous record, so a leaf issues all its loads at once instead of a chain of dependent ones.
-template <class R> struct SphereLeaf { SphereFilter f; SphereRec<R> s; int id, obj, mat, pad; };   // 64 B
+// kx: the expanded filter's record constant (filter_x_k; with f's centre, the SphereFilterX of the sphere)
+template <class R> struct SphereLeaf { SphereFilter f; SphereRec<R> s; int id, obj, mat; float kx; };   // 64 B
 template <> struct SphereLeaf<float> { SphereRec<float> s; int id, obj, mat, pad; };                 // 32 B
 // a triangle leaf carries only what the test reads (the winner's normal is read from TriRec by hit_record)
 template <class R> struct TriGeom { R v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z; };
@@ -509,6 +510,69 @@ RT_HD bool sphere_filter_pass(const SphereFilter& s, const FilterRay& r) {
     const float hb = __builtin_fmaf(ocx, r.dx, __builtin_fmaf(ocy, r.dy, ocz * r.dz));
     const float cc = __builtin_fmaf(ocx, ocx, __builtin_fmaf(ocy, ocy, __builtin_fmaf(ocz, ocz, -(s.r2p + r.delta))));
     return !(__builtin_fmaf(hb, hb, -cc) < 0.0f);
+}
+
+// The expanded filter (RT_FILTER_X; binary64 lean grid kernel, ACC_GRID_LDS_LEAN).  With oc = o - c multiplied
+// out, the three subtractions of sphere_filter_pass become constants of the ray and of the record:
+//   X' = (A - c32.dn)^2 + (2 o32.c32 + (k + B)),   A = o32.dn,  B = delta - |o32|^2  (per ray, binary32),
+//   k = r2p - |c32|^2 (per record: binary64 on the host from the record's own binary32 r2p and centre,
+//   rounded towards +inf; SphereLeaf::kx),
+// 3 FMA + 1 add + 3 FMA + 1 FMA + 1 compare = 9 VALU for the old form's 12.  In exact arithmetic X' is the X
+// of sphere_filter_bound.  Its rounding errors, in units of u Q (u = 2^-24, M_i = |o_i| + |c_i|, Q = sum
+// M_i^2 + r^2, as there; second-order terms are below 2^-20 of the first-order ones):
+//  h = A - c32.dn against OC.n: o and c rounded on input (u M_i per component), dn within 6.5u of n (as
+//    there), and six roundings (A's three-term FMA chain, then the three FMAs that subtract c32.dn), each at
+//    most u times a partial sum of magnitude <= sum M_i |dn_i| <= |M|(1 + 7u): |h - OC.n| <= (1 + 6.5 + 6) u
+//    |M| = 13.5u |M|, so |h^2 - (OC.n)^2| <= 27u |M|^2 <= 27u Q  (|OC.n| <= |M|, |M|^2 <= Q).
+//  e = 2 o32.c32 + (k + B) against -|OC|^2 + r2p + delta = -|o|^2 + 2 o.c - |c|^2 + r2p + delta:
+//    s = |o32|^2 (three roundings, 3u |o|^2; the input roundings of o, 2u |o|^2), delta = fl(s * const) is the
+//    value the bound is stated for, B = fl(delta - s) rounds by u |o|^2: |B - (delta - |o|^2)| <= 6u |o|^2;
+//    k exceeds r2p - |c32|^2 by at most one ulp, 2u (r2p + |c|^2), and |c32|^2 is within 2u |c|^2 of |c|^2:
+//    |k - (r2p - |c|^2)| <= 4u |c|^2 + 2u r2p;  fl(k + B) rounds by u (r2p + |c|^2 + |o|^2);
+//    the products 2 o32_i c32_i carry the input roundings, 4u sum |o_i||c_i|, and the three FMAs round by u
+//    times partial sums <= r2p + sum M_i^2: 3u Q.  With r2p <= (1 + 2^-15)(r^2 + 2^-16 |c|^2) and
+//    7|o|^2 + 5|c|^2 + 4 sum |o_i||c_i| <= 7 sum M_i^2:  |e - (..)| <= 7u sum M_i^2 + 3u r^2 + 3u Q <= 10u Q.
+//  The final FMA's rounding cannot change the sign.  So |X' - Y - (r2p - r^2) - delta| <= 37u Q (taken as 40u
+//  Q with the second-order terms), under half the margin r2p - r^2 + delta >= 128u Q: disc64 >= 0 implies
+//  X' > 0, and a rejected sphere is a sure binary64 miss.  NaN never rejects; a record whose k leaves
+//  binary32's range carries k = +inf (e is then +inf or NaN: never rejected).  tests/test_filter_x.py checks
+//  this on the old filter's adversarial cases, on |c|/r up to 10^6 and on origins on the sphere (worst
+//  observed 11.3u), and that rounding k down by 64 ulps or a wrong sign in the ray's constants is caught.
+// RT_FILTER_X: 0 the old filter everywhere (A/B); 1 the grid's LDS records (sphere_records_lds) in that kernel.
+// The dominant spheres' wave-uniform records stay on the old form: with them on the new one the kernel
+// measured the same.
+#ifndef RT_FILTER_X
+#define RT_FILTER_X 1
+#endif
+struct SphereFilterX { float cx, cy, cz, k; };                       // 16 B, the grid's LDS record
+struct FilterRayX { float ox2, oy2, oz2, dx, dy, dz, A, B; };       // ox2 = 2 o32.x, ...
+
+// k of a record, from the old record's binary32 centre and r2p: binary64 (the squares of binary32 numbers
+// are exact there, their sum and the difference round by 2^-52 relative, covered by the 2^-40 step), then
+// rounded to binary32 towards +inf
+inline float filter_x_k(const SphereFilter& f) {
+    const double c2 = ((double)f.cx * f.cx + (double)f.cy * f.cy) + (double)f.cz * f.cz;
+    const double kd = ((double)f.r2p - c2) + 0x1p-40 * ((double)f.r2p + c2);
+    if (!(fabs(kd) <= 3.4028234663852886e38)) return INFINITY;     // out of range (or NaN): never rejects
+    float k = (float)kd;
+    if ((double)k < kd) k = nextafterf(k, INFINITY);
+    return k;
+}
+RT_HD FilterRayX make_filter_ray_x(const FilterRay& f) {
+    FilterRayX x;
+    x.ox2 = f.ox + f.ox; x.oy2 = f.oy + f.oy; x.oz2 = f.oz + f.oz;
+    x.dx = f.dx; x.dy = f.dy; x.dz = f.dz;
+    x.A = __builtin_fmaf(f.ox, f.dx, __builtin_fmaf(f.oy, f.dy, f.oz * f.dz));
+    // f.delta = s * const with the same s (make_filter_ray)
+    x.B = f.delta - (f.ox * f.ox + f.oy * f.oy + f.oz * f.oz);
+    return x;
+}
+// false only if the sphere is certainly missed in binary64 (disc64 < 0): 9 VALU per sphere
+RT_HD bool sphere_filter_x_pass(const SphereFilterX& s, const FilterRayX& r) {
+    RT_HCOUNT(HC_FILTER_TESTS, 1);
+    const float h = __builtin_fmaf(-s.cx, r.dx, __builtin_fmaf(-s.cy, r.dy, __builtin_fmaf(-s.cz, r.dz, r.A)));
+    const float e = __builtin_fmaf(r.ox2, s.cx, __builtin_fmaf(r.oy2, s.cy, __builtin_fmaf(r.oz2, s.cz, s.k + r.B)));
+    return !(__builtin_fmaf(h, h, e) < 0.0f);
 }
 
 // Scene features a trace kernel is compiled for (FEAT template arguments; the lean kernels, kernel_select.h
@@ -1180,9 +1244,19 @@ RT_HD Closest<R> closest_hit_bvh(const SceneView<R>& sc, V3<R> o, V3<R> d, Work&
 #ifndef RT_GRID_COMPACT
 #define RT_GRID_COMPACT 1
 #endif
-template <class R>
+RT_HD bool lds_filter_pass(const rt_u4& q, const FilterRay& fr) {
+    SphereFilter f;
+    memcpy(&f, &q, sizeof f);
+    return sphere_filter_pass(f, fr);
+}
+RT_HD bool lds_filter_pass(const rt_u4& q, const FilterRayX& fr) {   // the LDS copy holds SphereFilterX records
+    SphereFilterX f;
+    memcpy(&f, &q, sizeof f);
+    return sphere_filter_x_pass(f, fr);
+}
+template <class R, class FR>
 RT_HD void sphere_records_lds(const rt_u4* lrec, const SphereLeaf<R>* recs, int first, int end, V3<R> o, V3<R> d,
-                              R a, const FilterRay& fr, R tmin, Closest<R>& b, float& tl, Work& w, R ya = (R)0,
+                              R a, const FR& fr, R tmin, Closest<R>& b, float& tl, Work& w, R ya = (R)0,
                               int origin = -1) {
     RT_COUNT(w.spheres += end - first);
     if constexpr (sizeof(R) == 8 && RT_GRID_COMPACT != 0) {
@@ -1191,9 +1265,7 @@ RT_HD void sphere_records_lds(const rt_u4* lrec, const SphereLeaf<R>* recs, int 
             uint32_t pass = 0;
             for (int i = 0; i < n; ++i) {                // (unrolled x2 / x4: -1.0 / -3.5 %)
                 const rt_u4 q = lrec[base + i];
-                SphereFilter f;
-                memcpy(&f, &q, sizeof f);
-                if (sphere_filter_pass(f, fr)) pass |= 1u << i;
+                if (lds_filter_pass(q, fr)) pass |= 1u << i;
             }
             while (pass) {
                 const int k = base + __builtin_ctz(pass);
@@ -1217,9 +1289,7 @@ RT_HD void sphere_records_lds(const rt_u4* lrec, const SphereLeaf<R>* recs, int 
         int id, obj, mat;
         if constexpr (sizeof(R) == 8) {
             const rt_u4 q = lrec[k];
-            SphereFilter f;
-            memcpy(&f, &q, sizeof f);
-            if (!sphere_filter_pass(f, fr)) continue;
+            if (!lds_filter_pass(q, fr)) continue;
             s = recs[k].s;
             id = recs[k].id; obj = recs[k].obj; mat = recs[k].mat;
         } else {
@@ -1245,11 +1315,17 @@ template <class R>
 RT_HD size_t grid_lds_bytes(const SceneView<R>& sc) {
     return grid_lds_rec_bytes(sc) + 4 * (size_t)(sc.num_grid_cells + 1);
 }
-template <class R>
+// XF: binary64 records in the expanded filter's form, {centre, kx} (the walk then takes a FilterRayX)
+template <class R, bool XF = false>
 RT_HD void copy_grid_lds(const SceneView<R>& sc, rt_u4* grec, int* gcell, int t, int threads) {
     const rt_u4* g = reinterpret_cast<const rt_u4*>(sc.grid_leaf);
     for (int k = t; k < sc.num_grid_recs; k += threads) {
-        if constexpr (sizeof(R) == 8) grec[k] = g[4 * k];               // the 16-B filter of a 64-B record
+        if constexpr (sizeof(R) == 8 && XF) {
+            rt_u4 q = g[4 * k];
+            q.w = g[4 * k + 3].w;                                       // SphereLeaf::kx in r2p's place
+            grec[k] = q;
+        }
+        else if constexpr (sizeof(R) == 8) grec[k] = g[4 * k];          // the 16-B filter of a 64-B record
         else { grec[2 * k] = g[2 * k]; grec[2 * k + 1] = g[2 * k + 1]; }
     }
     for (int k = t; k <= sc.num_grid_cells; k += threads) gcell[k] = sc.grid_cell[k];
@@ -1262,7 +1338,9 @@ struct GridRefs { const int* n; const float *lo, *hi, *cs, *ics; float far; };
 // FEAT: the scene features compiled in (Feat; the grid's lean kernel: spheres only)
 // LOCAL: sc is a local copy (closest_hit_acc's kernel-argument reload): its axis-indexed reads are
 // selects, not a private array indexed per lane
-template <class R, bool LDSG = false, int FEAT = F_ALL, bool LOCAL = false>
+// XF: the LDS copy holds the expanded filter's records (copy_grid_lds<R, true>; closest_hit_acc passes
+// grid_filter_x<R, ACC>(), the same constant the kernels stage their copy with)
+template <class R, bool LDSG = false, int FEAT = F_ALL, bool LOCAL = false, bool XF = false>
 RT_HD Closest<R> closest_hit_grid(const SceneView<R>& sc, V3<R> o, V3<R> d, Work& w, const BvhStack& stk, int origin = -1) {
     const R tmin = (R)0.001;
     Closest<R> b{(R)INFINITY, HIT_NONE, 0, 0, -1};
@@ -1271,6 +1349,11 @@ RT_HD Closest<R> closest_hit_grid(const SceneView<R>& sc, V3<R> o, V3<R> d, Work
     const R a = dot(d, d), ya = root_rcp(a);
     FilterRay fr{};
     if constexpr (sizeof(R) == 8) fr = make_filter_ray(o, d);
+    // the binary64 lean kernel (grid_filter_x): the expanded filter on the LDS records (copy_grid_lds<R, true>);
+    // the records read from memory (the dominant spheres, the far origin's sweep) keep the old one
+    static_assert(!XF || (sizeof(R) == 8 && LDSG), "the expanded filter reads binary64 LDS records");
+    FilterRayX fx{};
+    if constexpr (XF) fx = make_filter_ray_x(fr);
     if (sc.num_big_spheres > 0) sphere_records(sc.big_spheres, 0, sc.num_big_spheres, o, d, a, fr, tmin, b, tl, w, true, ya);
     if (sc.num_grid_cells <= 0) return b;
     const GridRefs gp{sc.grid_n, sc.grid_lo, sc.grid_hi, sc.grid_cs, sc.grid_ics, sc.grid_far};
@@ -1315,7 +1398,9 @@ RT_HD Closest<R> closest_hit_grid(const SceneView<R>& sc, V3<R> o, V3<R> d, Work
     for (;;) {
         RT_COUNT(++w.nodes);
         const int ci = cell[0] + gp.n[0] * (cell[1] + gp.n[1] * cell[2]);
-        if constexpr (LDSG) {
+        if constexpr (LDSG && XF) {
+            sphere_records_lds(stk.grec, sc.grid_leaf, stk.gcell[ci], stk.gcell[ci + 1], o, d, a, fx, tmin, b, tl, w, ya, origin);
+        } else if constexpr (LDSG) {
             sphere_records_lds(stk.grec, sc.grid_leaf, stk.gcell[ci], stk.gcell[ci + 1], o, d, a, fr, tmin, b, tl, w, ya, origin);
         } else {
 #if RT_GRID_UNIFORM && defined(__HIP_DEVICE_COMPILE__)
@@ -1375,6 +1460,11 @@ template <int ACC> constexpr int feat_of() {
          : ACC == ACC_BRUTE_NEE || ACC == ACC_BVH_STACK_NEE ? (F_ALL | F_TEX | F_LIGHT | F_NEE) : F_ALL;
 }
 
+// the kernels whose grid walk takes the expanded filter: their LDS copy is copy_grid_lds<R, true>'s
+template <class R, int ACC> constexpr bool grid_filter_x() {
+    return RT_FILTER_X != 0 && sizeof(R) == 8 && ACC == ACC_GRID_LDS_LEAN;
+}
+
 // RT_SC_RELOAD (bit mask of lean kernels: 1 tree, 2 grid, 4 brute force; default 2): the closest-hit
 // query's scene fields read from the kernel-argument segment at every query (a copy the compiler cannot
 // hoist) instead of kept in SGPRs across the segment loop, whose spills it reloads there by VALU
@@ -1411,7 +1501,7 @@ RT_HD Closest<R> closest_hit_acc(const SceneView<R>& sc, V3<R> o, V3<R> d, Work&
     else if constexpr (ACC == ACC_BVH_SPHERES_LDS) return closest_hit_bvh<R, true, false, true>(sc, o, d, w, stk);
     else if constexpr (ACC == ACC_GRID) return closest_hit_grid<R>(sc, o, d, w, stk);
     else if constexpr (ACC == ACC_GRID_LDS) return closest_hit_grid<R, true>(sc, o, d, w, stk);
-    else if constexpr (ACC == ACC_GRID_LDS_LEAN) return closest_hit_grid<R, true, feat_of<ACC>(), LOCAL>(sc, o, d, w, stk, origin);
+    else if constexpr (ACC == ACC_GRID_LDS_LEAN) return closest_hit_grid<R, true, feat_of<ACC>(), LOCAL, grid_filter_x<R, ACC>()>(sc, o, d, w, stk, origin);
     else if constexpr (ACC == ACC_BVH_STACK_LEAN)
         return closest_hit_bvh<R, true, true, false, false, feat_of<ACC>()>(sc, o, d, w, stk, skip_tri);
     else if constexpr (ACC == ACC_BVH_TRI_LDS) return closest_hit_bvh<R, true, true, false, true>(sc, o, d, w, stk);

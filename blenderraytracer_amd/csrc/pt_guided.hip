@@ -34,7 +34,7 @@ __device__ __forceinline__ BvhStack stage_walk_lds(const SceneView<R>& sc, unsig
     if constexpr (ACC == ACC_GRID_LDS || ACC == ACC_GRID_LDS_LEAN) {
         rt_u4* grec = reinterpret_cast<rt_u4*>(lds_dyn);
         int* gcell = reinterpret_cast<int*>(lds_dyn + grid_lds_rec_bytes(sc));
-        copy_grid_lds(sc, grec, gcell, threadIdx.x, 64);
+        copy_grid_lds<R, grid_filter_x<R, ACC>()>(sc, grec, gcell, threadIdx.x, 64);
         stk.gcell = gcell;
         stk.grec = grec;
     } else {

@@ -242,6 +242,12 @@ constexpr bool parks() { return RT_PARK != 0 && sizeof(R) == 8 && uses_stack<ACC
 #ifndef RT_DEFER_REGEN_TRI
 #define RT_DEFER_REGEN_TRI 48
 #endif
+// RT_TILE_SHIFT (pool_item of the binary64 lean grid kernel, where it measured +1.1 % on RTOW; the other LDS
+// kernels keep their code): a full tile's pixel coordinates by shifts instead of the software division by the
+// tile's width (0: the division for every tile, A/B)
+#ifndef RT_TILE_SHIFT
+#define RT_TILE_SHIFT 1
+#endif
 template <class R>
 __device__ __forceinline__ int defer_regen(const SceneView<R>& sc) {
     return sc.num_tri_nodes > 0 ? RT_DEFER_REGEN_TRI : RT_DEFER_REGEN;
@@ -450,10 +456,14 @@ __device__ __forceinline__ void pool_item(const TraceArgs<R>& args, double* __re
     Rng<R> g;
     V3<R> o, d, T;
     auto begin_item = [&](const uint32_t k) {
-        uint32_t sr;
+        uint32_t sr, mx, my;
+        // RT_TILE_SHIFT: a full tile (nv == 64, so vw == 8; wave-uniform) takes the pixel's place in the
+        // tile by shifts, a ragged one by the division by vw
         if (nv == 64) { m = k & 63; sr = k >> 6; }
         else { sr = k / (uint32_t)nv; m = k - sr * (uint32_t)nv; }
-        const int px = tl.x0 + (int)(m % (uint32_t)vw), py = tl.y0 + (int)(m / (uint32_t)vw);
+        if (RT_TILE_SHIFT && sizeof(R) == 8 && ACC == ACC_GRID_LDS_LEAN && nv == 64) { mx = m & 7; my = m >> 3; }
+        else { mx = m % (uint32_t)vw; my = m / (uint32_t)vw; }
+        const int px = tl.x0 + (int)mx, py = tl.y0 + (int)my;
         const int row = im.y0 + py;
         i = im.x0 + px;
         j = im.height - 1 - row;
@@ -590,7 +600,7 @@ void trace_pool_lds_kernel(const TraceArgs<R> args, double* __restrict__ part, c
     if constexpr (ACC == ACC_GRID_LDS || ACC == ACC_GRID_LDS_LEAN) {
         rt_u4* grec = reinterpret_cast<rt_u4*>(lds_dyn);
         int* gcell = reinterpret_cast<int*>(lds_dyn + grid_lds_rec_bytes(sc));
-        copy_grid_lds(sc, grec, gcell, threadIdx.x, 64 * W);
+        copy_grid_lds<R, grid_filter_x<R, ACC>()>(sc, grec, gcell, threadIdx.x, 64 * W);
         stk.gcell = gcell;
         stk.grec = grec;
     } else if constexpr (ACC == ACC_BVH_TRI_LDS) {
@@ -1266,7 +1276,7 @@ __device__ __forceinline__ BvhStack stage_lds_wave(const SceneView<R>& sc, unsig
     if constexpr (ACC == ACC_GRID_LDS || ACC == ACC_GRID_LDS_LEAN) {
         rt_u4* grec = reinterpret_cast<rt_u4*>(lds_dyn);
         int* gcell = reinterpret_cast<int*>(lds_dyn + grid_lds_rec_bytes(sc));
-        copy_grid_lds(sc, grec, gcell, threadIdx.x, 64);
+        copy_grid_lds<R, grid_filter_x<R, ACC>()>(sc, grec, gcell, threadIdx.x, 64);
         stk.gcell = gcell;
         stk.grec = grec;
     } else {

@@ -923,7 +923,7 @@ void make_records(const HostScene& hs, const rt_scene_desc& d, HostRecords<R>& o
     }
     auto leaf = [&](int id) {
         SphereLeaf<R> L{};
-        if constexpr (sizeof(R) == 8) L.f = out.sphere_filter[id];
+        if constexpr (sizeof(R) == 8) { L.f = out.sphere_filter[id]; L.kx = filter_x_k(L.f); }
         L.s = out.spheres[id];
         L.id = id;
         L.obj = hs.sphere_obj[id];

@@ -4,7 +4,7 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/blenderraytracer_amd/lib/variants
-SRCS="pt_trace.hip pt_onewave.hip rt_capi.cpp scene_json.cpp"   # the same sources (and per-source flags) as build.py
+SRCS="pt_trace.hip pt_onewave.hip pt_guided.hip rt_capi.cpp scene_json.cpp"  # the same sources (and per-source flags) as build.py
 mkdir -p "$OUT"
 for spec in "$@"; do
   name=${spec%%:*}; flags=${spec#*:}
