@@ -20,7 +20,7 @@ REPO = os.path.dirname(HERE)
 ARCH = os.environ.get("RT_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 
-SOURCES = ["pt_trace.hip", "pt_onewave.hip", "pt_guided.hip", "rt_capi.cpp", "scene_json.cpp"]
+SOURCES = ["pt_trace.hip", "pt_onewave.hip", "pt_guided.hip", "pt_error.hip", "rt_capi.cpp", "scene_json.cpp"]
 # per-source flags: the one-wave pool and lane-per-pixel kernels (pt_onewave.hip) with LLVM's AMDGPU
 # register-pressure trackers during scheduling (mesh50k +1.0 %, Cornell +1.4 %; the LDS kernels -3.6 %
 # with it, so not for pt_trace.hip)

@@ -106,6 +106,16 @@ class AovOutput(C.Structure):
                 ("kind", C.POINTER(C.c_int32)), ("index", C.POINTER(C.c_int32))]
 
 
+class ErrorStats(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("groups", C.c_int32), ("chunk_samples", C.c_int32), ("converged", C.c_int32),
+                ("pixels", C.c_int64), ("nonfinite_pixels", C.c_int64), ("frame_error", C.c_double),
+                ("max_error", C.c_double)]
+
+
+class ErrorOutput(C.Structure):
+    _fields_ = [("var_mean", C.POINTER(C.c_double)), ("rel_error", C.POINTER(C.c_float))]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_double, C.c_void_p)
 BAND_FN = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_void_p)   # rt_band_fn
 
@@ -145,6 +155,11 @@ EXPORTS = {
     "rt_emitter_samples": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint32),
                                      C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.POINTER(C.c_uint8)]),
+    "rt_scene_set_error_estimate": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rt_scene_set_noise_threshold": (C.c_int, [C.c_void_p, C.c_double, C.c_int32]),
+    "rt_error_stats_get": (C.c_int, [C.c_void_p, C.POINTER(ErrorStats)]),
+    "rt_error_estimate": (C.c_int, [C.c_void_p, C.POINTER(ErrorOutput)]),
+    "rt_error_estimate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/rt_scene_json.h (host-only scene-JSON loader)
     "rt_json_scene_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_json_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),

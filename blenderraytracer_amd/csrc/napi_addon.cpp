@@ -476,6 +476,13 @@ napi_value render(napi_env env, napi_callback_info info) {
             return throw_err(env, std::string("render: ") + rt_last_error());
         }
     }
+    // settings.errorEstimate: the per-pixel error estimate (rt_scene_set_error_estimate); settings.noiseThreshold /
+    // minSamples: the threshold stop (rt_scene_set_noise_threshold; needs the estimate).  Set here, like the filter
+    if (rt_scene_set_error_estimate(box->sc, get_num(env, s, "errorEstimate", 0) != 0 ? 1 : 0) != RT_OK ||
+        rt_scene_set_noise_threshold(box->sc, get_num(env, s, "noiseThreshold", 0.0), (int32_t)get_num(env, s, "minSamples", 0)) != RT_OK) {
+        delete job;
+        return throw_err(env, std::string("render: ") + rt_last_error());
+    }
     job->want_mean = get_num(env, s, "wantMean", 0) != 0;
     job->want_counts = get_num(env, s, "wantCounts", 0) != 0;
     job->want_post = get_num(env, s, "wantPost", 1) != 0;      // the post-gamma Float32 frame (default on)
@@ -585,6 +592,53 @@ napi_value aovs(napi_env env, napi_callback_info info) {
     return res;
 }
 
+// errorStats(scene) -> {samples, groups, chunkSamples, converged, pixels, nonfinitePixels, frameError, maxError}
+// (rt_error_stats_get): a host read, also inside onProgress (the worker waits for that call)
+napi_value error_stats(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    SceneBox* box = argc ? get_box(env, argv[0]) : nullptr;
+    if (!box || !box->sc) return throw_err(env, "errorStats(scene)");
+    rt_error_stats es{};
+    if (rt_error_stats_get(box->sc, &es) != RT_OK) return throw_err(env, rt_last_error());
+    napi_value res, v;
+    NAPI_OK(napi_create_object(env, &res));
+    const struct { const char* k; double v; } fields[] = {
+        {"samples", (double)es.samples}, {"groups", (double)es.groups}, {"chunkSamples", (double)es.chunk_samples},
+        {"converged", (double)es.converged}, {"pixels", (double)es.pixels}, {"nonfinitePixels", (double)es.nonfinite_pixels},
+        {"frameError", es.frame_error}, {"maxError", es.max_error}};
+    for (const auto& f : fields) {
+        napi_create_double(env, f.v, &v);
+        napi_set_named_property(env, res, f.k, v);
+    }
+    return res;
+}
+
+// errorEstimate(scene) -> {varMean: Float64Array(3 per pixel), relError: Float32Array} of the last render
+// (rt_error_estimate); throws "no estimate" without one
+napi_value error_estimate(napi_env env, napi_callback_info info) {
+    size_t argc = 1;
+    napi_value argv[1];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+    SceneBox* box = argc ? get_box(env, argv[0]) : nullptr;
+    if (!box || !box->sc) return throw_err(env, "errorEstimate(scene)");
+    if (box->busy) return throw_err(env, "errorEstimate: a render is in flight");
+    const size_t n = box->last_pixels;
+    napi_value ab_v, ab_r, var, rel, res;
+    void *pv = nullptr, *pr = nullptr;
+    NAPI_OK(napi_create_arraybuffer(env, 3 * n * sizeof(double), &pv, &ab_v));
+    NAPI_OK(napi_create_arraybuffer(env, n * sizeof(float), &pr, &ab_r));
+    const rt_error_output eo{static_cast<double*>(pv), static_cast<float*>(pr)};
+    if (rt_error_estimate(box->sc, &eo) != RT_OK) return throw_err(env, std::string("errorEstimate: ") + rt_last_error());
+    NAPI_OK(napi_create_typedarray(env, napi_float64_array, 3 * n, ab_v, 0, &var));
+    NAPI_OK(napi_create_typedarray(env, napi_float32_array, n, ab_r, 0, &rel));
+    NAPI_OK(napi_create_object(env, &res));
+    NAPI_OK(napi_set_named_property(env, res, "varMean", var));
+    NAPI_OK(napi_set_named_property(env, res, "relError", rel));
+    return res;
+}
+
 napi_value cancel(napi_env env, napi_callback_info info) {
     size_t argc = 1;
     napi_value argv[1];
@@ -670,6 +724,8 @@ napi_value init(napi_env env, napi_value exports) {
         {"createScene", nullptr, create_scene, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"render", nullptr, render, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"aovs", nullptr, aovs, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+        {"errorStats", nullptr, error_stats, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+        {"errorEstimate", nullptr, error_estimate, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"cancel", nullptr, cancel, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"checkpoint", nullptr, checkpoint, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"checkpointSamples", nullptr, checkpoint_samples, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

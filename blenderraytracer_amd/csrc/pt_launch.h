@@ -66,10 +66,13 @@ struct ReduceGate {
 
 // bvh: walk the BVHs (ACC_BVH_STACK, the ordered two-child walk), else World order (ACC_BRUTE).
 // pool: the sample-pool kernel (+ reduce_kernel when there are several chunks), else the lane-per-pixel
-// kernel (samples added in sample order, rt_settings.sum_order = RT_SUM_SAMPLE_ORDER)
+// kernel (samples added in sample order, rt_settings.sum_order = RT_SUM_SAMPLE_ORDER).
+// err_q (pool only): the error estimate's second moments (pt_error.h), n*3; every chunk, even a single one,
+// then goes through `part` (c.part must hold at least one chunk), and each launch's reduce is followed by
+// launch_error_moments_chunks of the same partials
 template <class R>
 hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Counters& c, bool bvh, bool pool,
-                        hipStream_t stream);
+                        hipStream_t stream, double* err_q = nullptr);
 
 // the sample pool's split of `ns` samples of a cw x ch crop: 8x8 tiles, samples per chunk, chunks and the
 // bytes of all chunk partials of one launch

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pt_launch.h"
+#include "pt_error.h"
 #include "kernel_select.h"
 #include "pool_order.h"
 #include "queue_slots.h"
@@ -1104,7 +1105,8 @@ static hipError_t launch_pool_kernel(const KernelChoice& k, const TraceArgs<R>& 
 }
 
 template <class R>
-static hipError_t launch_pool(const KernelChoice& k, const TraceArgs<R>& a0, bool count, hipStream_t stream) {
+static hipError_t launch_pool(const KernelChoice& k, const TraceArgs<R>& a0, bool count, hipStream_t stream,
+                              double* err_q = nullptr) {
     const ImageParams& im = a0.im;
     const int ns_all = im.s_end - im.s_begin;
     // the chunk choice depends on the scene, not on the walk, so BVH and brute force add the samples
@@ -1115,7 +1117,7 @@ static hipError_t launch_pool(const KernelChoice& k, const TraceArgs<R>& a0, boo
     // chunk partials that fit the scratch buffer; a frame that needs more is split into launches
     const size_t per_chunk = (size_t)tiles * kPartialBytesPerTile;
     int chunks_fit = chunks_all;
-    if (chunks_all > 1) {
+    if (chunks_all > 1 || err_q) {         // (the error estimate reads a single chunk from the partials, too)
         chunks_fit = (int)std::min<size_t>((size_t)chunks_all, a0.c.part ? a0.c.part_bytes / per_chunk : 0);
         if (chunks_fit < 1) return hipErrorInvalidValue;
     }
@@ -1126,13 +1128,16 @@ static hipError_t launch_pool(const KernelChoice& k, const TraceArgs<R>& a0, boo
         a.im.s_end = std::min(im.s_end, b + ns_max);
         const int ns = a.im.s_end - b, chunks = (ns + chunk - 1) / chunk;
         if ((long long)tiles * chunks > 0x7FFFFFFFLL) return hipErrorInvalidConfiguration;
-        double* part = chunks > 1 ? a0.c.part : nullptr;
+        double* part = chunks > 1 || err_q ? a0.c.part : nullptr;
         if (const hipError_t e = launch_pool_kernel(k, a, count, part, tiles, chunks, chunk, stream)) return e;
         if (part)
             hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)tiles), dim3(64), 0, stream, a.im, a.c.sum,
                                (const double*)part, tiles, chunks, (const uint32_t*)nullptr);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
+        if (err_q)                               // the chunk moments of the partials just added (pt_error.h)
+            if (const hipError_t em = launch_error_moments_chunks(a.im, err_q, part, tiles, chunks, chunk, ns, nullptr, stream))
+                return em;
     }
     return hipSuccess;
 }
@@ -1144,12 +1149,13 @@ template bool trace_walks_grid<float>(const SceneView<float>&);
 
 template <class R>
 hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Counters& c, bool bvh, bool pool,
-                        hipStream_t stream) {
+                        hipStream_t stream, double* err_q) {
     if (im.cw <= 0 || im.ch <= 0 || im.s_end <= im.s_begin) return hipSuccess;
+    if (err_q && !pool) return hipErrorInvalidValue;      // the estimate needs the pool's chunk partials
     const TraceArgs<R> a{sc, im, c};
     const bool count = c.segs || c.draws;
     const KernelChoice k = choose_kernel(sc, im.aa_mode, bvh, pool);
-    if (pool) return launch_pool(k, a, count, stream);
+    if (pool) return launch_pool(k, a, count, stream, err_q);
     return with_acc(k.acc, [&](auto tag) {
         constexpr int ACC = decltype(tag)::value;
         if constexpr (lds_form(ACC)) return hipErrorInvalidValue;      // pool launches only: never chosen here
@@ -1157,8 +1163,10 @@ hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Cou
     });
 }
 
-template hipError_t launch_trace<double>(const SceneView<double>&, const ImageParams&, const Counters&, bool, bool, hipStream_t);
-template hipError_t launch_trace<float>(const SceneView<float>&, const ImageParams&, const Counters&, bool, bool, hipStream_t);
+template hipError_t launch_trace<double>(const SceneView<double>&, const ImageParams&, const Counters&, bool, bool, hipStream_t,
+                                         double*);
+template hipError_t launch_trace<float>(const SceneView<float>&, const ImageParams&, const Counters&, bool, bool, hipStream_t,
+                                        double*);
 
 PoolPlan pool_plan(int cw, int ch, int ns, bool tri_bvh, int chunk) {
     PoolPlan p{0, 0, 0, 0};

@@ -21,6 +21,7 @@
 #include "../../include/rt_hip.h"
 #include "pt_launch.h"
 #include "pt_guided.h"
+#include "pt_error.h"
 #include "pool_order.h"
 #include "scene_pack.h"
 
@@ -195,7 +196,14 @@ constexpr int kCtlCancel = 128;
 constexpr int kMaxFused = 64;
 constexpr int kCtlFlag = kCtlCancel + kCancelCopies * kCancelStride;
 constexpr int kCtlFusedAborted = kCtlFlag + kMaxFused;
-constexpr int kCtlWords = kCtlFusedAborted + 2;
+// the error estimate (pt_error.h): the sticky `converged` word of the threshold stop, and one ErrorWords per
+// batch in flight (slot kb % ring, like the `aborted` words), 8-byte aligned
+constexpr int kCtlConverged = kCtlFusedAborted + 2;
+constexpr int kCtlErr = (kCtlConverged + 1 + 31) & ~31;
+constexpr int kErrSlots = kSlots * RT_MAX_DEVICES + kSlots;
+constexpr int kErrSlotWords = (int)(sizeof(ErrorWords) / sizeof(uint32_t));
+static_assert(sizeof(ErrorWords) % sizeof(uint32_t) == 0 && kErrSlotWords % 2 == 0, "ErrorWords slots stay 8-byte aligned");
+constexpr int kCtlWords = kCtlErr + kErrSlots * kErrSlotWords;
 static_assert(kCtlAborted + kSlots * RT_MAX_DEVICES + kSlots <= kCtlCancel, "one aborted word per ring slot");
 inline uint32_t ctl_load(const uint32_t* ctl, int k) { return __atomic_load_n(ctl + k, __ATOMIC_SEQ_CST); }
 inline void ctl_store(uint32_t* ctl, int k, uint32_t v) { __atomic_store_n(ctl + k, v, __ATOMIC_SEQ_CST); }
@@ -414,6 +422,16 @@ struct rt_scene {
     DevBuf<float> guides;
     hipEvent_t g_used = nullptr;
     bool g_used_recorded = false;
+    // the error estimate (rt_scene_set_error_estimate, pt_error.h).  err_q: the pixels' second moments of the
+    // samples home.sum holds (err_valid), err_groups chunk partials each; err_tile: the frame reduction's tile
+    // partials; err_var / err_rel: rt_error_estimate's staging.  err_stats: the figures complete() read last
+    bool err_on = false, err_valid = false;
+    double err_threshold = 0.0;
+    int err_min_samples = 0, err_groups = 0, err_samples = 0;
+    DevBuf<double> err_q, err_tile, err_var;
+    DevBuf<float> err_rel;
+    CkptKey err_key{};              // the frame err_q is of (its crop: the estimate kernels' indexing)
+    rt_error_stats err_stats{};
     size_t ckpt_pixels = 0;         // progressive state of the last rt_render / rt_render_resume:
     int ckpt_done = 0;              // `home.sum` holds samples [sample_begin, ckpt_done) of ckpt_pixels pixels
     CkptKey ckpt_key{};             // ... of this frame, crop, first sample, precision and seed
@@ -625,18 +643,49 @@ int check_accel(const rt_scene* sc, const rt_settings* s) {
 bool use_pool(const rt_settings* s) { return s->sum_order == RT_SUM_POOL && trace_uses_pool(); }
 
 hipError_t trace(const rt_scene* sc, const DeviceState& ds, const rt_settings* s, const ImageParams& im,
-                 const Counters& c, hipStream_t st) {
+                 const Counters& c, hipStream_t st, double* err_q = nullptr) {
     if (im.max_depth <= 0) return hipSuccess;   // rayColor(ray, depth<=0) is 0: nothing to trace
     const bool bvh = use_bvh(sc, s), pool = use_pool(s);
-    return with_view(ds, s->precision, [&](const auto& v) { return launch_trace(v, im, c, bvh, pool, st); });
+    return with_view(ds, s->precision, [&](const auto& v) { return launch_trace(v, im, c, bvh, pool, st, err_q); });
+}
+
+// The error estimate's launches after a batch's reduce, on the reduce's (home) stream and under its gate
+// (render_impl; pt_error.h): the chunk moments of the partials just added (part == nullptr: launch_trace added
+// them), then the frame's figures over the `samples` samples and `groups` chunk partials the sums hold once this
+// batch is in, written to the batch's ErrorWords slot — and, with a threshold, the stop of every later batch.
+// Before whatever lets the partials be overwritten (the slot's `reduced` event, the stage's `stage_free`).
+struct ErrorBatch { int groups, samples, slot; };
+hipError_t error_after_reduce(rt_scene* sc, const ErrorBatch& eb, const ImageParams& im, const double* part,
+                              const ReduceGate* gate, hipStream_t st) {
+    const uint32_t* skip = gate ? gate->skip : nullptr;
+    hipError_t e = hipSuccess;
+    if (part) e = launch_error_moments(im, sc->err_q.p, part, sc->tri_bvh, skip, st);
+    if (e == hipSuccess && eb.groups >= 2)
+        e = launch_error_estimate(im, sc->home.sum.p, sc->err_q.p, eb.groups, eb.samples, nullptr, nullptr, sc->err_tile.p,
+                                  skip, st);
+    if (e != hipSuccess) return e;
+    ErrorFrame f{};
+    f.tiles = ((im.cw + 7) / 8) * ((im.ch + 7) / 8);
+    f.groups = eb.groups;
+    f.samples = eb.samples;
+    f.min_samples = sc->err_min_samples;
+    f.pixels = (long long)im.cw * im.ch;
+    f.threshold = gate ? sc->err_threshold : 0.0;      // only a gated render can stop
+    f.tile_part = sc->err_tile.p;
+    f.out = reinterpret_cast<ErrorWords*>(sc->ctl_dev + kCtlErr + eb.slot * kErrSlotWords);
+    f.stop = sc->ctl_dev + kCtlStop;
+    f.converged = sc->ctl_dev + kCtlConverged;
+    f.skip = skip;
+    return launch_error_frame(f, st);
 }
 
 // One overlapped batch on one device: the pool kernel writes the batch's chunk partials into slot `j`
 // on tstream[j] (after the reduce that last read slot j), and `stream` adds them to the sums in chunk
 // order once the trace is done.  Sums see the same additions in the same order as trace() of the batch
 // (bit-identical), while the trace of batch k+1 may already run beside batch k's draining waves.
-hipError_t trace_overlapped(const rt_scene* sc, DeviceState& ds, const rt_settings* s, const ImageParams& im,
-                            const Counters& c, int j, bool slot_used, const ReduceGate* gate) {
+hipError_t trace_overlapped(rt_scene* sc, DeviceState& ds, const rt_settings* s, const ImageParams& im,
+                            const Counters& c, int j, bool slot_used, const ReduceGate* gate,
+                            const ErrorBatch* eb = nullptr) {
     if (im.max_depth <= 0 || im.s_end <= im.s_begin) return hipSuccess;
     const bool bvh = use_bvh(sc, s);
     DevBuf<double>& part = ds.slot_part(j);
@@ -650,6 +699,7 @@ hipError_t trace_overlapped(const rt_scene* sc, DeviceState& ds, const rt_settin
     if (e == hipSuccess) e = hipEventRecord(ds.traced[j], ts);
     if (e == hipSuccess) e = hipStreamWaitEvent(ds.stream, ds.traced[j], 0);
     if (e == hipSuccess) e = launch_reduce(im, c.sum, part.p, sc->tri_bvh, ds.stream, gate);
+    if (e == hipSuccess && eb) e = error_after_reduce(sc, *eb, im, part.p, gate, ds.stream);
     if (e == hipSuccess) e = hipEventRecord(ds.reduced[j], ds.stream);
     return e;
 }
@@ -662,7 +712,7 @@ hipError_t trace_overlapped(const rt_scene* sc, DeviceState& ds, const rt_settin
 // are bit-identical to the same batches on one device.  The replica's next trace into slot j follows
 // the copy on the same stream.
 int trace_replica(rt_scene* sc, DeviceState& ds, MergeSlot& m, const rt_settings* s, const ImageParams& im,
-                  const Counters& c, int j, const ReduceGate* gate) {
+                  const Counters& c, int j, const ReduceGate* gate, const ErrorBatch* eb = nullptr) {
     if (im.max_depth <= 0 || im.s_end <= im.s_begin) return RT_OK;
     DeviceState& h = sc->home;
     const int cw = im.cw, ch = im.ch;
@@ -683,6 +733,7 @@ int trace_replica(rt_scene* sc, DeviceState& ds, MergeSlot& m, const rt_settings
     HIP_TRY(hipSetDevice(h.device));
     HIP_TRY(hipStreamWaitEvent(h.stream, ds.traced[j], 0));
     HIP_TRY(launch_reduce(im, h.sum.p, m.stage[j].p, sc->tri_bvh, h.stream, gate));
+    if (eb) HIP_TRY(error_after_reduce(sc, *eb, im, m.stage[j].p, gate, h.stream));
     HIP_TRY(hipEventRecord(m.stage_free[j], h.stream));
     m.stage_used[j] = true;
     return RT_OK;
@@ -757,12 +808,14 @@ hipError_t scratch_idle(DeviceState& ds) {
     return ds.scratch_used ? hipEventSynchronize(ds.scratch_ev) : hipSuccess;
 }
 
+// single: a launch of one chunk gets its partials too (the error estimate reads them, launch_trace's err_q)
 int ensure_partials(const rt_scene* sc, DeviceState& ds, int cw, int ch, int samples, bool pool, Counters& c,
-                    int chunk = 0) {
+                    int chunk = 0, bool single = false) {
     if (!pool || samples <= 0 || cw <= 0 || ch <= 0) return RT_OK;
-    const size_t want_all = pool_partial_bytes(cw, ch, samples, sc->tri_bvh, chunk);
-    if (want_all == 0) return RT_OK;
     const size_t per_chunk = (size_t)((cw + 7) / 8) * ((ch + 7) / 8) * kPartialBytesPerTile;
+    size_t want_all = pool_partial_bytes(cw, ch, samples, sc->tri_bvh, chunk);
+    if (want_all == 0 && single) want_all = per_chunk;
+    if (want_all == 0) return RT_OK;
     size_t want = want_all;
     if (want > ds.part.n * sizeof(double)) {
         HIP_TRY(scratch_idle(ds));
@@ -996,6 +1049,7 @@ void rt_scene_destroy(rt_scene* sc) {
     (void)hipSetDevice(sc->home.device);
     sc->mean.release(); sc->post.release(); sc->post_raw.release();
     sc->g_mean.release(); sc->g_ping.release(); sc->g_pong.release(); sc->guides.release();
+    sc->err_q.release(); sc->err_tile.release(); sc->err_var.release(); sc->err_rel.release();
     if (sc->g_used) (void)hipEventDestroy(sc->g_used);
     for (MergeSlot& m : sc->merge) m.release();
     sc->rgba.release();
@@ -1113,6 +1167,14 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
     if (!rc) rc = check_accel(sc, s);
     if (!rc) rc = check_guided(sc, s, cw, ch);
     if (rc) return rc;
+    // the error estimate reads the sample pool's chunk partials: renders without them are refused while it is on
+    if (sc->err_on) {
+        if (s->sum_order != RT_SUM_POOL)
+            return fail(RT_ERR_INVALID, "the error estimate needs the sample pool (RT_SUM_SAMPLE_ORDER has no chunk partials)");
+        if (!use_pool(s)) return fail(RT_ERR_INVALID, "the error estimate needs the sample pool (it is switched off)");
+        if (s->max_depth <= 0) return fail(RT_ERR_INVALID, "the error estimate needs max_depth > 0 (nothing is traced)");
+    } else if (sc->err_threshold > 0.0)
+        return fail(RT_ERR_INVALID, "a noise threshold needs the error estimate on");
     std::vector<DeviceState*> states;
     if ((rc = shard_states(sc, s, states))) return rc;
     // no checkpoint from here until the new sums are consistent (set below, with the samples they hold):
@@ -1235,6 +1297,37 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
             fused = ensure_fused(*states[d], fdoubles, (nb - d + nsh - 1) / nsh);
         }
     }
+    // The error estimate of this render (pt_error.h): rt_render starts it, a resident resume of a render that
+    // has one continues it; a resume from host sums (or from sums without moments) leaves none
+    const bool err_active = sc->err_on && !sums_in && (!resident || (sc->err_valid && sc->err_key == ckpt_key(s, cw, ch)));
+    std::vector<int> groups_after(nb, 0);         // chunk partials per pixel once batch kb is in
+    int err_chunk = 0;
+    if (sc->err_on) {
+        if (nsh > 1 && !whole)
+            return fail(RT_ERR_INVALID, "the error estimate needs whole batches per device (this render splits every "
+                        "batch's samples over the devices)");
+        if (sc->err_threshold > 0.0 && nb > 1 && !gated)
+            return fail(RT_ERR_INVALID, "the noise threshold needs overlapped batches (their commit gates stop the render)");
+        if (!resident) sc->err_groups = sc->err_samples = 0;
+        sc->err_valid = err_active && resident;
+        if (!err_active || !resident) sc->err_stats = rt_error_stats{};
+        ctl_store(sc->ctl, kCtlConverged, 0);
+    }
+    if (err_active) {
+        int g = sc->err_groups;
+        for (int kb = 0; kb < nb; ++kb) {
+            const int b = s0 + kb * batch, ns = std::min(s1, b + batch) - b;
+            const PoolPlan p = pool_plan(cw, ch, ns, sc->tri_bvh, fused ? fchunk : batch_chunk(whole ? kb % nsh : 0, ns));
+            if (kb == 0) err_chunk = p.chunk;
+            groups_after[kb] = g += p.chunks;
+        }
+        HIP_TRY(hipSetDevice(h.device));
+        HIP_TRY(sc->err_q.ensure(3 * n));
+        HIP_TRY(sc->err_tile.ensure(3 * (size_t)((cw + 7) / 8) * ((ch + 7) / 8)));
+        sc->err_key = ckpt_key(s, cw, ch);
+        if (nb > 0) sc->err_stats.chunk_samples = err_chunk;
+        else err_chunk = sc->err_stats.chunk_samples;
+    }
     bool fused_launched = false;
     for (int k = 0; k < nsh; ++k) {
         DeviceState& ds = *states[k];
@@ -1246,7 +1339,8 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         int b0, b1;
         shard_range(s0, s0 + std::min(batch, s1 - s0), k, nsh, b0, b1);
         const int ns = std::max(1, b1 - b0);
-        if (!overlap && s->max_depth > 0 && (rc = ensure_partials(sc, ds, cw, ch, ns, pool, c, batch_chunk(k, ns)))) return rc;
+        if (!overlap && s->max_depth > 0 && (rc = ensure_partials(sc, ds, cw, ch, ns, pool, c, batch_chunk(k, ns), err_active)))
+            return rc;
         HIP_TRY(order_scratch(ds, ds.stream));
         if (resident && &ds == &h) {
             // the scene's checkpoint is already in place
@@ -1288,6 +1382,7 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         }
     }
     HIP_TRY(hipSetDevice(h.device));
+    if (err_active && !resident) HIP_TRY(hipMemsetAsync(sc->err_q.p, 0, 3 * n * sizeof(double), h.stream));
     if ((int)sc->batch_done.size() < ring) sc->batch_done.resize(ring, nullptr);
     for (hipEvent_t& e : sc->batch_done)
         if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1345,13 +1440,20 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         static const bool fused_preview_env = getenv("RT_FUSED_PREVIEW") && getenv("RT_FUSED_PREVIEW")[0] == '1';
         const bool fuse_prev = fused && fused_preview_env && want_preview && be < s1 && thresholds;
         bool previewed = false;
+        // the error estimate's launches follow the batch's reduce, under its gate (error_after_reduce)
+        const ErrorBatch eb{err_active ? groups_after[kb] : 0, be - base, kb % ring};
+        const ErrorBatch* ebp = err_active ? &eb : nullptr;
         auto reduce_batch = [&](const ImageParams& bi, const double* src) -> hipError_t {
-            if (!fuse_prev) return launch_reduce(bi, h.sum.p, src, sc->tri_bvh, h.stream, gp);
-            FinalizeParams fp{(int)n, be - base, s->tone_map, s->exposure, s->gamma};
-            hipError_t e = launch_reduce_preview(bi, h.sum.p, src, sc->tri_bvh, h.stream, gp, fp, thresholds->table(),
-                                                 sc->preview_dev[kb % ring]);
-            if (e == hipSuccess) e = gamma_used(thresholds, h.stream);
-            previewed = e == hipSuccess;
+            hipError_t e;
+            if (!fuse_prev) e = launch_reduce(bi, h.sum.p, src, sc->tri_bvh, h.stream, gp);
+            else {
+                FinalizeParams fp{(int)n, be - base, s->tone_map, s->exposure, s->gamma};
+                e = launch_reduce_preview(bi, h.sum.p, src, sc->tri_bvh, h.stream, gp, fp, thresholds->table(),
+                                          sc->preview_dev[kb % ring]);
+                if (e == hipSuccess) e = gamma_used(thresholds, h.stream);
+                previewed = e == hipSuccess;
+            }
+            if (e == hipSuccess && ebp) e = error_after_reduce(sc, eb, bi, src, gp, h.stream);
             return e;
         };
         auto with_cancel = [&](Counters c) {
@@ -1445,8 +1547,8 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
             bi.pool_chunk = batch_chunk(k, be - b);
             HIP_TRY(hipSetDevice(ds.device));
             slots_used[k] |= 1u << j;
-            if (&ds == &h) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(cs[k]), j, lj >= kSlots, gp));
-            else if (int r = trace_replica(sc, ds, sc->merge[k], s, bi, with_cancel(cs[k]), j, gp)) return r;
+            if (&ds == &h) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(cs[k]), j, lj >= kSlots, gp, ebp));
+            else if (int r = trace_replica(sc, ds, sc->merge[k], s, bi, with_cancel(cs[k]), j, gp, ebp)) return r;
         }
         for (int k = 0; k < nsh && !whole && !fused; ++k) { // every shard's launches first: the devices run together
             DeviceState& ds = *states[k];
@@ -1454,8 +1556,11 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
             shard_range(b, be, k, nsh, bi.s_begin, bi.s_end);
             bi.pool_chunk = batch_chunk(k, bi.s_end - bi.s_begin);
             HIP_TRY(hipSetDevice(ds.device));
-            if (overlap) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(cs[k]), kb % kSlots, kb >= kSlots, gp));
-            else HIP_TRY(trace(sc, ds, s, bi, cs[k], ds.stream));
+            if (overlap) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(cs[k]), kb % kSlots, kb >= kSlots, gp, ebp));
+            else {                                // (the estimate: one device, launch_trace adds the chunk moments)
+                HIP_TRY(trace(sc, ds, s, bi, cs[k], ds.stream, ebp ? sc->err_q.p : nullptr));
+                if (ebp) HIP_TRY(error_after_reduce(sc, eb, bi, nullptr, nullptr, ds.stream));
+            }
         }
         int r;
         if (nsh > 1 && !whole && (r = merge_shards(sc, states, n, want_segs, want_draws))) return r;
@@ -1474,12 +1579,31 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
     };
     // host side of batch kb once batch_done: checkpoint state and the preview frame.  merged: the batch
     // is in the sums (gated renders: not if a cancel left it unfinished)
+    // the error figures of committed batch kb, from its slot of the control words
+    auto err_commit = [&](int kb) {
+        __atomic_thread_fence(__ATOMIC_SEQ_CST);
+        ErrorWords w;
+        memcpy(&w, sc->ctl + kCtlErr + (kb % ring) * kErrSlotWords, sizeof w);
+        rt_error_stats& st = sc->err_stats;
+        st.samples = w.samples;
+        st.groups = w.groups;
+        st.chunk_samples = err_chunk;
+        st.converged = ctl_load(sc->ctl, kCtlConverged) ? 1 : 0;
+        st.pixels = w.pixels;
+        st.nonfinite_pixels = w.nonfinite;
+        st.frame_error = w.frame_error;
+        st.max_error = w.max_error;
+        sc->err_groups = w.groups;
+        sc->err_samples = w.samples;
+        sc->err_valid = true;
+    };
     auto complete = [&](int kb, bool& merged) -> int {
         HIP_TRY(hipEventSynchronize(sc->batch_done[kb % ring]));
         const int be = std::min(s1, s0 + (kb + 1) * batch);
         merged = !gated || (int)ctl_load(sc->ctl, kCtlDone) >= be;
         if (!merged) return RT_OK;
         sc->ckpt_done = be;
+        if (err_active) err_commit(kb);
         // the running frame, unless the next batch has finished too (its frame supersedes this one: the
         // host does not fall further behind the GPU copying frames nobody will see)
         if (want_preview && be < s1 &&
@@ -1493,6 +1617,7 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
     // partial slots is device-side: trace_overlapped), so neither the host's progress call nor a preview
     // frame ever delays the start of a batch
     int status = RT_OK;
+    bool stopped = false;                         // the noise threshold ended the render early
     auto fill = [&](int upto) -> int {          // enqueue batches [enqueued, upto)
         for (; enqueued < std::min(upto, nb) && !sc->cancel.load(); ++enqueued) {
             const int r = enqueue(enqueued);
@@ -1504,7 +1629,10 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         if ((status = fill(kb + (fused ? 0 : ahead) + 1))) break;   // fused: enqueue(kb) waits for batch kb
         bool merged = true;
         if ((status = complete(kb, merged))) break;
-        if (!merged && !sc->cancel.load()) {
+        // the threshold stop (error_frame_kernel set `stop` and `converged` after an earlier batch): the gates
+        // skip every later batch, and nobody cancelled
+        const bool conv = err_active && gated && ctl_load(sc->ctl, kCtlConverged) != 0;
+        if (!merged && !sc->cancel.load() && !conv) {
             // a gate skipped a batch although nobody cancelled (rt_cancel sets `cancel` before the word the
             // kernels read): an item-count mismatch or a lost flag — an internal failure, not a cancel
             status = fail(RT_ERR_DEVICE, "batch %d was not committed (internal error)", kb);
@@ -1515,7 +1643,7 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
             sc->cancel.store(1);
             ctl_cancel(sc->ctl, 1);
         }
-        if (!merged || sc->cancel.load()) {
+        if (!merged || sc->cancel.load() || (conv && be < s1)) {
             if (gated) {
                 // the queued batches stop at their next item and are not reduced; once every stream has
                 // drained, the sums hold exactly the batches the gates committed
@@ -1524,6 +1652,7 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
                 for (DeviceState* ds : states) ds->sync_all();
                 h.sync_all();
                 sc->ckpt_done = (int)ctl_load(sc->ctl, kCtlDone);
+                if (err_active && sc->ckpt_done > s0) err_commit((sc->ckpt_done - s0 + batch - 1) / batch - 1);
                 if (want_preview && sc->ckpt_done > base && sc->ckpt_done < s1) {   // the checkpoint's frame
                     HIP_TRY(hipSetDevice(h.device));
                     FinalizeParams fp{(int)n, sc->ckpt_done - base, s->tone_map, s->exposure, s->gamma};
@@ -1536,8 +1665,10 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
                 // the batches in flight finish (and if the last one was among them, the render completed)
                 for (int k = kb + 1; k < enqueued && status == RT_OK; ++k) status = complete(k, merged);
             }
-            if (status == RT_OK && sc->ckpt_done < s1)
-                status = fail(RT_ERR_CANCELLED, "render cancelled after %d samples", sc->ckpt_done);
+            if (status == RT_OK && sc->ckpt_done < s1) {
+                if (conv && !sc->cancel.load() && sc->ckpt_done > base) stopped = true;   // RT_OK over the samples done
+                else status = fail(RT_ERR_CANCELLED, "render cancelled after %d samples", sc->ckpt_done);
+            }
             break;
         }
     }
@@ -1585,6 +1716,10 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
     HIP_TRY(hipSetDevice(h.device));
     HIP_TRY(hipStreamSynchronize(h.stream));          // the merges of the last batch (checkpoint state)
     if (status != RT_OK) return status;
+    if (stopped) {                                // the epilogue and the statistics over the samples committed
+        s_local.samples = sc->ckpt_done - base;
+        im.s_end = sc->ckpt_done;
+    }
     const bool want_mean = out && out->mean, want_post = out && out->post, want_rgba = out && out->rgba8;
     if (want_mean) HIP_TRY(sc->mean.ensure(3 * n));
     if (want_post) HIP_TRY(sc->post.ensure(4 * n));
@@ -2099,6 +2234,65 @@ int rt_guided_filter_device(rt_scene* sc, int32_t width, int32_t height, const r
     HIP_TRY(guided_scratch_begin(sc, st));
     HIP_TRY(guided_levels(width, height, *p, d_color, d_guides, d_out, sc->g_ping.p, st));
     HIP_TRY(guided_scratch_end(sc, st));
+    return RT_OK;
+}
+
+int rt_scene_set_error_estimate(rt_scene* sc, int32_t on) {
+    if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
+    if ((on != 0) != sc->err_on) {                   // a switch either way leaves no estimate (and no threshold when off)
+        sc->err_valid = false;
+        sc->err_groups = sc->err_samples = 0;
+        sc->err_stats = rt_error_stats{};
+    }
+    sc->err_on = on != 0;
+    if (!sc->err_on) {
+        sc->err_threshold = 0.0;
+        sc->err_min_samples = 0;
+    }
+    return RT_OK;
+}
+
+int rt_scene_set_noise_threshold(rt_scene* sc, double threshold, int32_t min_samples) {
+    if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (threshold != threshold) return fail(RT_ERR_INVALID, "noise threshold is NaN");
+    if (threshold > 0.0 && !sc->err_on) return fail(RT_ERR_INVALID, "a noise threshold needs the error estimate on");
+    sc->err_threshold = threshold > 0.0 ? threshold : 0.0;
+    sc->err_min_samples = std::max(0, min_samples);
+    return RT_OK;
+}
+
+int rt_error_stats_get(rt_scene* sc, rt_error_stats* stats) {
+    if (!sc || !stats) return fail(RT_ERR_INVALID, "NULL argument");
+    *stats = sc->err_stats;
+    return RT_OK;
+}
+
+int rt_error_estimate_device(rt_scene* sc, double* d_var_mean, float* d_rel_error, void* hip_stream) {
+    if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
+    if (!sc->err_on || !sc->err_valid || sc->err_groups < 2 || sc->err_samples <= 0 || sc->ckpt_pixels == 0 ||
+        !(sc->err_key == sc->ckpt_key))
+        return fail(RT_ERR_INVALID, "no estimate (%d groups)", sc->err_valid ? sc->err_groups : 0);
+    ImageParams im{};
+    im.cw = sc->err_key.cw;
+    im.ch = sc->err_key.ch;
+    HIP_TRY(hipSetDevice(sc->home.device));
+    HIP_TRY(launch_error_estimate(im, sc->home.sum.p, sc->err_q.p, sc->err_groups, sc->err_samples, d_var_mean, d_rel_error,
+                                  nullptr, nullptr, (hipStream_t)hip_stream));
+    return RT_OK;
+}
+
+int rt_error_estimate(rt_scene* sc, const rt_error_output* out) {
+    if (!sc || !out) return fail(RT_ERR_INVALID, "NULL argument");
+    const size_t n = sc->ckpt_pixels;
+    HIP_TRY(hipSetDevice(sc->home.device));
+    if (out->var_mean && n) HIP_TRY(sc->err_var.ensure(3 * n));
+    if (out->rel_error && n) HIP_TRY(sc->err_rel.ensure(n));
+    hipStream_t st = sc->home.stream;
+    if (int rc = rt_error_estimate_device(sc, out->var_mean ? sc->err_var.p : nullptr, out->rel_error ? sc->err_rel.p : nullptr, st))
+        return rc;
+    if (out->var_mean) HIP_TRY(hipMemcpyAsync(out->var_mean, sc->err_var.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (out->rel_error) HIP_TRY(hipMemcpyAsync(out->rel_error, sc->err_rel.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
 }
 

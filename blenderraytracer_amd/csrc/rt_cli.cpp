@@ -6,7 +6,12 @@
 //                 [--accel auto|bvh|brute] [--frames K] [--warmup W] [--batch B] [--device N]
 //                 [--out image.ppm|image.pam] [--lights] [--nee]
 //                 [--guided] [--guided-levels N] [--guided-sigma C,A,N,Z] [--aovs PREFIX]
+//                 [--noise T] [--min-spp N]
 //
+// --noise T: stop at the first progress batch after which the frame's estimated error (rt_error_stats.frame_error)
+// is at or under T; --min-spp N: not before N samples.  Either implies the error estimate
+// (rt_scene_set_error_estimate) and at least 16 progress batches (--batch B is kept when it gives that many);
+// the JSON line then carries samples_done, frame_error and converged
 // --guided: the edge-aware guided filter over the linear mean (rt_scene_set_guided; --guided-levels and
 // --guided-sigma colour,albedo,normal,depth override the defaults and imply it)
 // --aovs PREFIX: the feature buffers of the primary hit (rt_aovs) as PREFIX.albedo.pfm, PREFIX.normal.pfm (colour
@@ -76,12 +81,14 @@ int main(int argc, char** argv) {
         fprintf(stderr, "usage: rt_render_cli scene.json [--width W --height H --spp S --depth D --seed N --aa MODE "
                         "--tone MAP --exposure E --gamma G --denoise STRENGTH --precision f64|f32 --accel auto|bvh|brute "
                         "--frames K --warmup W --batch B --device N --out FILE --lights --nee --guided --guided-levels N "
-                        "--guided-sigma C,A,N,Z --aovs PREFIX]\n");
+                        "--guided-sigma C,A,N,Z --aovs PREFIX --noise T --min-spp N]\n");
         return argc < 2 ? 2 : 0;
     }
     const char* scene_path = argv[1];
     int width = 800, height = 600, frames = 1, warmup = 0, batch = 0, device = 0;
-    double spp = 4, depth = 5, exposure = 1.0, gamma = 2.2, denoise = 0;
+    double spp = 4, depth = 5, exposure = 1.0, gamma = 2.2, denoise = 0, noise = 0;
+    int min_spp = 0;
+    bool estimate = false;
     uint32_t seed = 1;
     std::string aa = "supersampling", tone = "reinhard", precision = "f64", accel = "auto", out, aovs;
     bool lights = false, guided = false, nee = false;
@@ -112,6 +119,8 @@ int main(int argc, char** argv) {
         else if (a == "--device") device = atoi(v);
         else if (a == "--out") out = v;
         else if (a == "--aovs") aovs = v;
+        else if (a == "--noise") { noise = atof(v); estimate = true; }
+        else if (a == "--min-spp") { min_spp = atoi(v); estimate = true; }
         else if (a == "--guided-levels") { gp.levels = atoi(v); guided = true; }
         else if (a == "--guided-sigma") {
             if (sscanf(v, "%lf,%lf,%lf,%lf", &gp.sigma_color, &gp.sigma_albedo, &gp.sigma_normal, &gp.sigma_depth) != 4)
@@ -148,6 +157,12 @@ int main(int argc, char** argv) {
     s.precision = precision == "f32" ? RT_PREC_F32 : RT_PREC_F64;
     s.accel = accel == "bvh" ? RT_ACCEL_BVH : (accel == "brute" ? RT_ACCEL_BRUTE : RT_ACCEL_AUTO);
     s.batch_samples = batch;
+    if (estimate) {
+        // at least 16 progress batches for the threshold to act on (-16: about 16, sized to the pool's chunks)
+        if (batch <= 0 || (s.samples + batch - 1) / batch < 16) s.batch_samples = -16;
+        check(rt_scene_set_error_estimate(scene, 1), "--noise");
+        check(rt_scene_set_noise_threshold(scene, noise, min_spp), "--noise");
+    }
     if (denoise > 0) {                                       // post-processor.js:55 weights, host exp
         s.denoise = 1;
         s.denoise_weights[0] = jsm::exp(-1.0 / (2 * denoise * denoise));   // V8's Math.exp (post-processor.js:60)
@@ -160,23 +175,33 @@ int main(int argc, char** argv) {
     rt_stats st{};
     for (int k = 0; k < warmup; ++k) check(rt_render(scene, &s, &o, nullptr, nullptr, &st), "rendering");
     double wall = 0, kernel = 0;
-    uint64_t segments = 0, nodes = 0;
+    uint64_t segments = 0, nodes = 0, traced = 0;
     for (int k = 0; k < frames; ++k) {
         const double t0 = now_ms();
         check(rt_render(scene, &s, &o, nullptr, nullptr, &st), "rendering");
         wall += now_ms() - t0;
         kernel += st.kernel_ms;
         segments += st.segments;
+        traced += st.samples;                                // (fewer than n * spp when --noise stopped the frame)
         nodes += st.node_visits;
     }
-    const double samples = (double)n * s.samples * frames;
+    const double samples = (double)traced;
+    rt_error_stats es{};
+    if (estimate) check(rt_error_stats_get(scene, &es), "--noise");
     printf("{\"scene\": \"%s\", \"width\": %d, \"height\": %d, \"spp\": %d, \"max_depth\": %d, \"precision\": \"%s\", "
            "\"accel\": \"%s\", \"frames\": %d, \"msamples_per_s\": %.3f, \"kernel_msamples_per_s\": %.3f, "
            "\"ms_per_frame\": %.3f, \"kernel_ms_per_frame\": %.3f, \"upload_ms\": %.3f, \"segments_per_sample\": %.4f, "
-           "\"bvh_nodes_per_segment\": %.3f}\n",
+           "\"bvh_nodes_per_segment\": %.3f",
            scene_path, width, height, s.samples, s.max_depth, precision.c_str(), accel.c_str(), frames,
            samples / (wall * 1e-3) / 1e6, samples / (kernel * 1e-3) / 1e6, wall / frames, kernel / frames, upload_ms,
            segments / samples, segments ? (double)nodes / segments : 0.0);
+    if (estimate) {                                         // the last frame's: samples done and the frame's error
+        printf(", \"samples_done\": %d, \"converged\": %d, \"error_groups\": %d, \"frame_error\": ", es.samples, es.converged,
+               es.groups);
+        if (es.frame_error == es.frame_error) printf("%.17g", es.frame_error);
+        else printf("null");
+    }
+    printf("}\n");
     if (!out.empty()) {
         FILE* f = fopen(out.c_str(), "wb");
         if (!f) die("cannot write ", out.c_str());

@@ -69,7 +69,29 @@ export function settingsOf(rt, opts = {}) {
         // the edge-aware guided filter over the linear mean (opt-in): the RayTracer's own members (GpuRayTracer),
         // else the options (installGpuRender on a reference RayTracer); unset parameters take the library's defaults
         ...guidedOf(rt, opts),
+        // the per-pixel error estimate (opt-in) and the noise-threshold stop, which implies it (INTEGRATION.md §11)
+        errorEstimate: (opts.errorEstimate || opts.noiseThreshold > 0 || opts.minSamples > 0) ? 1 : 0,
+        noiseThreshold: opts.noiseThreshold > 0 ? opts.noiseThreshold : 0,
+        minSamples: opts.minSamples > 0 ? opts.minSamples : 0,
     };
+}
+
+// render(onProgress), render(onProgress, {noiseThreshold, minSamples}) or render({noiseThreshold, minSamples,
+// onProgress}): the progress callback and the per-render options
+function renderArgs(a, b) {
+    if (a && typeof a === 'object') return { onProgress: a.onProgress, extra: a };
+    return { onProgress: a, extra: b || {} };
+}
+
+// rt_error_stats of the RayTracer's scene on the GPU (null before its first render): samples, groups, chunkSamples,
+// converged, pixels, nonfinitePixels, frameError, maxError.  A host read: may be called inside onProgress.
+export function gpuErrorStats(rt) {
+    return rt.__gpuScene ? loadNative().errorStats(rt.__gpuScene.scene) : null;
+}
+// {varMean: Float64Array (3 per pixel), relError: Float32Array} of the last render; throws without an estimate
+export function gpuErrorEstimate(rt) {
+    if (!rt.__gpuScene) throw new Error('errorEstimate: no render yet');
+    return loadNative().errorEstimate(rt.__gpuScene.scene);
 }
 
 function guidedOf(rt, opts) {
@@ -214,15 +236,22 @@ function blit(rt, res) {
 // opts: {seed, precision: 'f64'|'f32', accel, batchSamples | progressSteps (default 16), device,
 //        devices: [HIP ordinals], sumOrder: 'pool' | 'sample',
 //        directLighting: render this.world.lights (the reference's own PointLight / DirectionalLight objects),
-//        keepFloatData: also read back the post-gamma Float32 frame into this.floatData}
+//        keepFloatData: also read back the post-gamma Float32 frame into this.floatData,
+//        errorEstimate: keep the per-pixel error estimate (errorStats(), errorEstimate()),
+//        noiseThreshold, minSamples: stop at the first progress batch whose frame error is at or under the
+//        threshold, not before minSamples samples (implies errorEstimate; also per render: render(onProgress,
+//        {noiseThreshold, minSamples}) or render({noiseThreshold, minSamples, onProgress}))}
 export function installGpuRender(rayTracer, opts = {}) {
-    rayTracer.render = async function render(onProgress) {
-        const res = await gpuRender(this, onProgress, { ...opts, intoImageData: true, wantPost: !!opts.keepFloatData });
+    rayTracer.render = async function render(a, b) {
+        const { onProgress, extra } = renderArgs(a, b);
+        const res = await gpuRender(this, onProgress, { ...opts, ...extra, intoImageData: true, wantPost: !!opts.keepFloatData });
         if (!res) return;
         blit(this, res);
         this.lastStats = res.stats;
         if (onProgress) onProgress(1.0);
     };
+    rayTracer.errorStats = function errorStats() { return gpuErrorStats(this); };
+    rayTracer.errorEstimate = function errorEstimate() { return gpuErrorEstimate(this); };
     return rayTracer;
 }
 
@@ -289,13 +318,19 @@ export class GpuRayTracer {
         this.world.solidColor = new Vec3(0.1, 0.1, 0.1);
     }
 
-    async render(onProgress) {
-        const res = await gpuRender(this, onProgress, { ...this.opts, intoImageData: true, wantPost: !!this.opts.keepFloatData });
+    // render(onProgress) as the reference's; render(onProgress, {noiseThreshold, minSamples}) or render({noiseThreshold,
+    // minSamples, onProgress}) stop at the noise threshold (the error estimate: opts.errorEstimate, or implied)
+    async render(a, b) {
+        const { onProgress, extra } = renderArgs(a, b);
+        const res = await gpuRender(this, onProgress, { ...this.opts, ...extra, intoImageData: true, wantPost: !!this.opts.keepFloatData });
         if (!res) return;
         blit(this, res);
         this.lastStats = res.stats;
         if (onProgress) onProgress(1.0);
     }
+
+    errorStats() { return gpuErrorStats(this); }
+    errorEstimate() { return gpuErrorEstimate(this); }
 
     // Continue the last cancelled render (window.renderCancelled) from its checkpoint.
     async resume(onProgress) {

@@ -59,10 +59,12 @@ GUIDED_SIGMAS = dict(capi.RT_GUIDED_DEFAULT_SIGMAS)
 
 class GpuRayTracer:
     def __init__(self, width, height, seed=0, device=0, precision=capi.RT_PREC_F64, accel=capi.RT_ACCEL_AUTO,
-                 sum_order=capi.RT_SUM_POOL, direct_lighting=False, emitter_sampling=False):
+                 sum_order=capi.RT_SUM_POOL, direct_lighting=False, emitter_sampling=False, error_estimate=False):
         self.width, self.height = int(width), int(height)
         self.direct_lighting = bool(direct_lighting)   # opt-in: render World.lights
         self.emitter_sampling = bool(emitter_sampling)  # opt-in: sample emissive geometry with MIS
+        # opt-in: the per-pixel error estimate from the sample pool's chunk partials
+        self.error_estimate_on = bool(error_estimate)
         self.seed = seed
         self.device = device
         self.precision = precision
@@ -215,7 +217,31 @@ class GpuRayTracer:
         capi.check(lib.rt_aovs(scene, C.byref(st), C.byref(out)))
         return res
 
-    def render(self, on_progress=None, crop=None, want=("rgba8",), batch_samples=0, resume=None, devices=None):
+    def _apply_error_estimate(self, lib, scene, noise_threshold=0.0, min_samples=0):
+        capi.check(lib.rt_scene_set_error_estimate(scene, 1 if self.error_estimate_on else 0))
+        capi.check(lib.rt_scene_set_noise_threshold(scene, float(noise_threshold), int(min_samples)))
+
+    def error_stats(self):
+        """rt_error_stats_get as a dict: samples, groups, chunk_samples, converged, pixels, nonfinite_pixels,
+        frame_error, max_error of the last committed batch (host read only: may be called inside on_progress)."""
+        st = capi.ErrorStats()
+        capi.check(capi.load_library().rt_error_stats_get(self.scene_handle(), C.byref(st)))
+        return {k: getattr(st, k) for k, _ in capi.ErrorStats._fields_}
+
+    def error_estimate(self, crop=None):
+        """(var_mean (h, w, 3) float64, rel_error (h, w) float32) of the last render (rt_error_estimate): the estimated
+        variance of every pixel's mean per channel and sqrt(sum var) / (sum mean + 0.03).  RuntimeError
+        (RT_ERR_INVALID, "no estimate") without at least two chunk partials per pixel."""
+        st = self.settings(crop=crop)
+        cw, ch = st.crop_w or self.width, st.crop_h or self.height
+        var = np.zeros((ch, cw, 3), dtype=np.float64)
+        rel = np.zeros((ch, cw), dtype=np.float32)
+        out = capi.ErrorOutput(var.ctypes.data_as(C.POINTER(C.c_double)), rel.ctypes.data_as(C.POINTER(C.c_float)))
+        capi.check(capi.load_library().rt_error_estimate(self.scene_handle(), C.byref(out)))
+        return var, rel
+
+    def render(self, on_progress=None, crop=None, want=("rgba8",), batch_samples=0, resume=None, devices=None,
+               noise_threshold=0.0, min_samples=0):
         """RayTracer.render: fills image_data (RGBA8) and float_data (post-gamma RGBA float).
         Returns a dict of the requested host arrays (mean, post, rgba8, segments, draws, preview, and the
         feature buffers albedo, normal, depth of render_aovs).
@@ -224,10 +250,15 @@ class GpuRayTracer:
         "preview" in want (with batch_samples): when on_progress runs, image_data (full frame) and the
         returned "preview" array hold the frame of the samples done so far (rt_output.preview_rgba8); a
         cancel (on_progress returning True, or rt_cancel) leaves the frame of the checkpointed samples
-        there and raises RuntimeError(RT_ERR_CANCELLED)."""
+        there and raises RuntimeError(RT_ERR_CANCELLED).
+        noise_threshold, min_samples (GpuRayTracer(error_estimate=True), with batch_samples): stop at the first batch
+        after which the frame's estimated error (error_stats()["frame_error"]) is at or under the threshold and at
+        least min_samples samples are in; the result is the frame of the samples done (last_stats.samples,
+        error_stats()), and checkpoint() may resume it.  resume = (None, done): from the sums still on the device."""
         lib = capi.load_library()
         scene = self.scene_handle()
         self._apply_guided(lib, scene)
+        self._apply_error_estimate(lib, scene, noise_threshold, min_samples)
         st = self.settings(crop=crop, batch_samples=batch_samples, devices=devices)
         cw = st.crop_w or self.width
         ch = st.crop_h or self.height
@@ -258,10 +289,11 @@ class GpuRayTracer:
             rc = lib.rt_render(scene, C.byref(st), C.byref(out), cb, None, C.byref(stats))
         else:
             sums, done = resume
-            sums = np.ascontiguousarray(sums, dtype=np.float64)
-            assert sums.size == 3 * n, "checkpoint of another frame size"
-            rc = lib.rt_render_resume(scene, C.byref(st), sums.ctypes.data_as(C.POINTER(C.c_double)), int(done),
-                                      C.byref(out), cb, None, C.byref(stats))
+            if sums is not None:
+                sums = np.ascontiguousarray(sums, dtype=np.float64)
+                assert sums.size == 3 * n, "checkpoint of another frame size"
+            rc = lib.rt_render_resume(scene, C.byref(st), None if sums is None else sums.ctypes.data_as(C.POINTER(C.c_double)),
+                                      int(done), C.byref(out), cb, None, C.byref(stats))
         if rc == -4 and "preview" in want and crop is None:    # cancelled: the frame of the checkpoint stays
             self.image_data = res["preview"]
         capi.check(rc)

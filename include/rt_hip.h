@@ -474,6 +474,56 @@ int rt_scene_emitter_count(rt_scene* scene, int32_t* count);
 int rt_emitter_samples(rt_scene* scene, int32_t precision, int32_t accel, const double* points, const uint32_t* keys,
                        size_t n, int32_t* emitter, double* omega, double* p_l, double* t_e, uint8_t* visible);
 
+/* Per-pixel error estimate and the noise-threshold stop (DESIGN.md §4 "Error estimate"): an
+ * append-only extension of generation 3.  Off by default; while off, renders run exactly as before.
+ *
+ * The sample pool writes one partial sum per pixel and chunk of samples.  While the estimate is on, every batch's
+ * reduce is followed by a pass that adds S_c^2 / n_c of every chunk to a per-pixel second moment q (binary64,
+ * 3 per pixel, on the scene's device) under the batch's commit gate, so the moments cover exactly the samples
+ * the sums hold.  With K chunks over N samples and S their sum, B = q - S^2 / N has expectation (K - 1) sigma^2
+ * whatever the chunk sizes; var_mean = max(0, B) / ((K - 1) N) estimates the variance of the pixel's mean per
+ * channel.  A pixel's relative error is e_p = sqrt(sum_ch var_mean) / (sum_ch mean + 0.03); the frame's error is
+ * the mean of e_p over the pixels whose sums and moments are finite.  A pixel with a non-finite sum or moment
+ * has NaN in every channel and is counted in nonfinite_pixels.
+ *
+ * rt_render zeroes the moments; rt_render_resume with sums NULL continues them; a resume from host sums leaves
+ * no estimate.  rt_render / rt_render_resume return RT_ERR_INVALID while the estimate is on and the render has
+ * no chunk partials: RT_SUM_SAMPLE_ORDER (or the pool switched off), max_depth <= 0, or several devices that
+ * split every batch's samples (whole batches per device are supported).  rt_trace_device and
+ * rt_trace_device_bands never produce an estimate.  Not to be switched while a render is in flight. */
+int rt_scene_set_error_estimate(rt_scene* scene, int32_t on);
+/* Stop a progressive render at the first batch after which frame_error <= threshold and the estimate covers at
+ * least min_samples samples (counted from sample_begin).  threshold <= 0: off (the default).  A threshold > 0
+ * needs the estimate on (RT_ERR_INVALID otherwise, here and in rt_render).  The decision is taken on the device
+ * in stream order (it sets the word the later batches' commit gates read), so the batch a render stops at does
+ * not depend on host timing.  The stopped render drains like a cancelled one, runs the normal epilogue over the
+ * samples committed (mean = sum / samples done; guided filter, tone map and denoise as configured), reports
+ * them in rt_stats.samples, leaves the checkpoint there (a resume may continue to the full count) and returns
+ * RT_OK.  A render of one batch has nothing to stop; a threshold with several batches that do not overlap on
+ * the device (RT_OVERLAP=0, or no memory for the partial slots) is RT_ERR_INVALID. */
+int rt_scene_set_noise_threshold(rt_scene* scene, double threshold, int32_t min_samples);
+typedef struct rt_error_stats {
+    int32_t samples;            /* samples (from sample_begin) the estimate covers = the committed batches */
+    int32_t groups;             /* K, chunk partials accumulated per pixel (< 2: no estimate, the figures are NaN) */
+    int32_t chunk_samples;      /* the pool's chunk for this render */
+    int32_t converged;          /* 1: the frame met the threshold (the render stopped there unless it was its last batch) */
+    int64_t pixels, nonfinite_pixels;
+    double frame_error, max_error;
+} rt_error_stats;
+/* The figures after the last committed batch the host has seen.  Host read only: may be called inside
+ * progress() (the figures of the batch just reported).  groups = 0 when there is no estimate at all. */
+int rt_error_stats_get(rt_scene* scene, rt_error_stats* stats);
+typedef struct rt_error_output {
+    double* var_mean;           /* n*3, may be NULL */
+    float* rel_error;           /* n, may be NULL */
+} rt_error_output;
+/* The per-pixel estimate of the last render, between renders.  RT_ERR_INVALID ("no estimate") when groups < 2,
+ * when there has been no render since the estimate was switched on, or after a resume from host sums. */
+int rt_error_estimate(rt_scene* scene, const rt_error_output* out);
+/* The same into device buffers (either may be NULL), asynchronous on hip_stream: it reads the scene's sums and
+ * moments, so the caller orders it before the scene's next render. */
+int rt_error_estimate_device(rt_scene* scene, double* d_var_mean, float* d_rel_error, void* hip_stream);
+
 /* Request cancellation of an in-flight rt_render on `scene` (the pool kernels read it between items;
  * see rt_render). */
 int rt_cancel(rt_scene* scene);
