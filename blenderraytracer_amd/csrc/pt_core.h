@@ -835,10 +835,25 @@ RT_HD bool tri_filter_pass(const TriFilter& f, const TriRay& r, float tl) {
 // |bound - o| per axis (rounded o, d, 1/d and the product), which the same margins cover, and the
 // ray-length limit is (float)t_best rounded up by 2^-20.  So a node holding a primitive that beats
 // the current best is never culled; f64 mode stays bit-identical to the brute-force walk
-// (tests/test_hostcheck.py, tests/test_gpu_parity.py).  Directions with a binary32-denormal
-// component are clamped to 1/d = 2^126 (t ranges beyond 2^100 are not modelled).
+// (tests/test_hostcheck.py, tests/test_gpu_parity.py, tests/test_sphere_walks.py).
 // The two-child walk evaluates (lo - olo) * inv as fma(lo, inv, -olo * inv): one rounding of olo*inv
-// more, an error < 2^-23 (|o| + |lo|) |inv| in t, still 16x inside the same margins.
+// more, an error < 2^-23 (|o| + |lo|) |inv| in t, still 16x inside the same margins.  That form needs
+// slo = olo * inv finite: with slo = +-inf the FMA is inf - inf = NaN for any |lo| |inv| >= 2^128, the
+// min / max of the slab test drop or spread the NaN, and the node is culled although the ray crosses it
+// (a zero component, inv = 2^126, from |o| = 4 on; any |o / d| beyond binary32's range).
+// Steep components.  Every 1/d_k, clamped or not, is therefore limited to |inv| <= L = 2^126 / max(|o|_inf, 1)
+// (zero and binary32-denormal components included: their reciprocal is +-inf or beyond L).  Then
+// |olo * inv| <= (|o|_inf + pad) L < 2^127 is finite, and an FMA of finite operands is NaN-free: it rounds
+// the exact lo * inv - slo once and overflows, if at all, to the infinity of the right sign.
+// What a limited axis still models: it stands for a direction component d' with |d'| = 1/L >= |d_k|.  A
+// primitive of the node accepted at t has lo <= o_k + t d_k <= hi up to the margins above, so
+// lo - olo <= t d_k - pad and hi - ohi >= t d_k + pad.  For t <= pad L the step |t d_k| <= t / L <= pad, so
+// lo - olo <= 0 <= hi - ohi: the axis' interval contains 0, hence max(0, .) on the near side, and its far
+// end is at least pad L >= t for either sign of inv.  The axis never culls such a hit.  pad L is at least
+// 2^107 min(|o|_inf, 1) and at least 2^26, so: hits at t <= max(2^26, 2^107 min(|o|_inf, 1)) are modelled
+// for every finite ray (|o|_inf < 2^127), whatever its direction; on an axis that is not limited the test
+// is the plain slab test, as before.  Larger t with a limited component (a direction some 2^26 below unit
+// length that also has a component 2^100 below its length) is not modelled, as it never was.
 struct BvhRay { float olo[3], ohi[3], inv[3], slo[3], shi[3]; };   // slo = olo * inv, shi = ohi * inv
 
 template <class R>
@@ -848,11 +863,12 @@ RT_HD BvhRay make_bvh_ray(V3<R> o, V3<R> d) {
     const float df[3] = {(float)d.x, (float)d.y, (float)d.z};
     const float m = fmaxf(fabsf(of[0]), fmaxf(fabsf(of[1]), fabsf(of[2])));
     const float pad = m * (0x1p-19f * (1.0f + 0x1p-20f)) + 0x1p-100f;
+    const float lim = 0x1p126f * rt_rcp_approx(fmaxf(m, 1.0f));    // L, within 2^-22 (once per ray, not per node)
     for (int k = 0; k < 3; ++k) {
         r.olo[k] = of[k] + pad;      // (lo - olo) * inv and (hi - ohi) * inv widen the slab for both signs of d
         r.ohi[k] = of[k] - pad;
         float inv = rt_rcp_approx(df[k]);
-        if (!(fabsf(inv) <= 0x1p126f)) inv = copysignf(0x1p126f, df[k]);
+        if (!(fabsf(inv) <= lim)) inv = copysignf(lim, df[k]);
         r.inv[k] = inv;
         r.slo[k] = r.olo[k] * inv;
         r.shi[k] = r.ohi[k] * inv;
@@ -1209,6 +1225,22 @@ RT_HD Closest<R> closest_hit_bvh(const SceneView<R>& sc, V3<R> o, V3<R> d, Work&
             bvh_walk<WIDE, TLDS ? 2 : 0>(sc.tri_nodes, sc.num_tri_nodes, sc.tri_wide, br, tl, stk, w, leaf);
         }
     }
+    // The winner's material by its index, not as the leaf loops carried it.  A tree visits primitives in leaf
+    // order, so of two exactly coincident spheres the later one in World order may be met first; the earlier one
+    // then wins through `better`'s tie clause.  On the device the binary64 kernels returned that winner's t, idx
+    // and obj with the other sphere's material (rt_closest_hits: World.hit's index on every ray; rt_aovs: that
+    // index with the other sphere's albedo; renders: the other sphere's shading, tests/test_sphere_walks_gpu.py,
+    // `hollow`).  The gfx950 code of sphere_records' loop shows why the fields can part although the source
+    // assigns them together: the compiler splits the struct, moves the record's material into the best hit's
+    // register ahead of the tie test and puts the old value back for every lane that fails t < best, the lanes
+    // that then accept on the tie included, while t, idx and obj are written in the acceptance block itself.
+    // The remedy does not depend on that diagnosis: the material is a function of (kind, idx), idx is the
+    // value every consumer already trusts, and after this line nothing reads what the loops kept.  The grid
+    // and World order are left as they were: they meet coincident spheres in World order (cells and the
+    // dominant list hold ascending indices, the dominant of equal radii is the first), so the earlier sphere
+    // is accepted by t < best and the later one fails the tie clause; no acceptance is by a tie.
+    if (b.kind == HIT_SPHERE) b.mat = sc.sphere_mat[b.idx];
+    else if (TRI && b.kind == HIT_TRI) b.mat = sc.tri_mat[b.idx];
     return b;
 }
 

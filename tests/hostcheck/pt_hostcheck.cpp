@@ -298,6 +298,55 @@ extern "C" long long ptc_bvh_check(const rt_scene_desc* d, long long n, unsigned
     return bad;
 }
 
+// Closest hits of n caller-supplied rays (origin xyz, direction xyz) through one sphere walk, binary64
+// (tests/test_sphere_walks.py compares each with tests/sphere_ref.py): walk 0 World order, 1 the ordered
+// two-child walk, 2 the stackless walk, 3 closest_hit_grid, 4 its LDS-copy form, 5 its lean LDS form with
+// the expanded filter.  t = +inf and idx = -1 on a miss.  Returns -2 when the scene has no grid for 3..5.
+extern "C" int ptc_walk_hits(const rt_scene_desc* d, int walk, const double* rays, long long n, double* t, int* idx) {
+    HostView<double> hv;
+    if (!hv.init(d)) return -1;
+    const SceneView<double>& v = hv.v;
+    if (walk >= 3 && (v.num_grid_cells <= 0 || v.num_tri_nodes > 0)) return -2;
+    std::vector<rt_u4> grec(grid_lds_rec_bytes(v) / 16 + 1);
+    std::vector<int> gcell((size_t)v.num_grid_cells + 1);
+    if (walk == 4) copy_grid_lds<double>(v, grec.data(), gcell.data(), 0, 1);
+    if (walk == 5) copy_grid_lds<double, true>(v, grec.data(), gcell.data(), 0, 1);
+    int stack[64];
+    BvhStack stk{stack, 1};
+    stk.gcell = gcell.data();
+    stk.grec = grec.data();
+    for (long long k = 0; k < n; ++k) {
+        const double* r = rays + 6 * k;
+        const V3<double> O{r[0], r[1], r[2]}, D{r[3], r[4], r[5]};
+        Work w{};
+        const Closest<double> c = walk == 0 ? closest_hit<double>(v, O, D)
+                                : walk == 1 ? closest_hit_bvh<double, true>(v, O, D, w, stk)
+                                : walk == 2 ? closest_hit_bvh<double, false>(v, O, D, w, BvhStack{nullptr, 0})
+                                : walk == 3 ? closest_hit_grid<double>(v, O, D, w, stk)
+                                : walk == 4 ? closest_hit_grid<double, true>(v, O, D, w, stk)
+                                            : closest_hit_grid<double, true, 0, false, true>(v, O, D, w, stk);
+        t[k] = c.kind == HIT_NONE ? INFINITY : c.t;
+        idx[k] = c.kind == HIT_NONE ? -1 : c.idx;
+    }
+    return 0;
+}
+
+// The grid's binary32 geometry as the walk reads it (build_grid): out = {lo xyz, cell size xyz, grid_far};
+// n3 = cells per axis (0 0 0: no grid); *largest = the most records registered in one cell
+extern "C" int ptc_grid_geometry(const rt_scene_desc* d, double* out, int* n3, int* largest) {
+    HostView<double> hv;
+    if (!hv.init(d)) return -1;
+    for (int k = 0; k < 3; ++k) {
+        out[k] = hv.hs.grid_lo[k];
+        out[3 + k] = hv.hs.grid_cs[k];
+        n3[k] = hv.hs.grid_n[k];
+    }
+    out[6] = hv.hs.grid_far;
+    *largest = 0;
+    for (size_t c = 0; c + 1 < hv.hs.grid_cell.size(); ++c) *largest = std::max(*largest, hv.hs.grid_cell[c + 1] - hv.hs.grid_cell[c]);
+    return 0;
+}
+
 // BVH shape: deepest leaf of the binary trees, their two-child node count, and the dominant spheres
 // tested before the walk (their sphere indices into big[0..*nbig), at most 8 written)
 extern "C" int ptc_bvh_info(const rt_scene_desc* d, int* depth, int* nodes2, int* nbig, int* big) {

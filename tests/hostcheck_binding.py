@@ -90,6 +90,36 @@ def bvh_rays(packed, n, seed, host_n=None):
     return rays[:m], t[:m], kind[:m], idx[:m]
 
 
+WALKS = ("world", "two_child", "stackless", "grid", "grid_lds", "grid_lds_lean")
+
+
+def walk_hits(packed, walk, rays):
+    """Binary64 closest hits (t, sphere index; +inf and -1 on a miss) of n x 6 rays through one of WALKS (the
+    kernel's own code compiled for the CPU); None when the scene has no grid for a grid walk."""
+    L = lib()
+    L.ptc_walk_hits.argtypes = [C.POINTER(capi.SceneDesc), C.c_int, C.POINTER(C.c_double), C.c_longlong,
+                                C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    t = np.full(len(rays), np.nan)
+    idx = np.full(len(rays), -2, dtype=np.int32)
+    rc = L.ptc_walk_hits(C.byref(packed.desc), WALKS.index(walk), rays.ctypes.data_as(C.POINTER(C.c_double)), len(rays),
+                         t.ctypes.data_as(C.POINTER(C.c_double)), idx.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc == -2:
+        return None
+    assert rc == 0
+    return t, idx
+
+
+def grid_geometry(packed):
+    """build_grid's result as the walk reads it: dict(lo, cs (binary32 values), n (cells per axis; zeros: no
+    grid), far (grid_far), largest (most records in one cell))."""
+    L = lib()
+    L.ptc_grid_geometry.argtypes = [C.POINTER(capi.SceneDesc), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    out, n3, largest = (C.c_double * 7)(), (C.c_int * 3)(), C.c_int()
+    assert L.ptc_grid_geometry(C.byref(packed.desc), out, n3, C.byref(largest)) == 0
+    return {"lo": np.array(out[0:3]), "cs": np.array(out[3:6]), "far": out[6], "n": np.array(n3[:]), "largest": largest.value}
+
+
 EVENTS = ["f64_sphere_tests", "disc_nonneg", "second_root", "accept", "lambertian", "metal", "dielectric", "emissive",
           "miss", "samples", "sphere_draw_rounds", "disk_draw_rounds", "filter_tests", "dielectric_schlick",
           "tri_filter_tests", "tri_tests"]
