@@ -17,6 +17,7 @@ RT_MAX_DEVICES = 8
 RT_GUIDED_MAX_LEVELS = 8
 RT_GUIDED_DEFAULT_LEVELS = 5
 RT_GUIDED_DEFAULT_SIGMAS = {"color": 1.0, "albedo": 0.1, "normal": 0.35, "depth": 0.05}   # RT_GUIDED_DEFAULT_SIGMA_*
+RT_GUIDED_DEFAULT_SIGMA_VARIANCE = 4.0
 
 # enums (include/rt_hip.h)
 RT_OBJ_SPHERE, RT_OBJ_PLANE, RT_OBJ_BOX, RT_OBJ_TRIANGLE, RT_OBJ_MESH = range(5)
@@ -160,6 +161,10 @@ EXPORTS = {
     "rt_error_stats_get": (C.c_int, [C.c_void_p, C.POINTER(ErrorStats)]),
     "rt_error_estimate": (C.c_int, [C.c_void_p, C.POINTER(ErrorOutput)]),
     "rt_error_estimate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_scene_set_guided_variance": (C.c_int, [C.c_void_p, C.c_double]),
+    "rt_guided_filter_variance_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GuidedParams), C.c_double,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_guided_filtered_variance": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     # include/rt_scene_json.h (host-only scene-JSON loader)
     "rt_json_scene_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_json_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),

@@ -478,7 +478,15 @@ napi_value render(napi_env env, napi_callback_info info) {
     }
     // settings.errorEstimate: the per-pixel error estimate (rt_scene_set_error_estimate); settings.noiseThreshold /
     // minSamples: the threshold stop (rt_scene_set_noise_threshold; needs the estimate).  Set here, like the filter
-    if (rt_scene_set_error_estimate(box->sc, get_num(env, s, "errorEstimate", 0) != 0 ? 1 : 0) != RT_OK ||
+    // settings.guidedVariance / guidedSigmaVariance: the filter's variance-guided form (rt_scene_set_guided_variance);
+    // it reads the estimate, so it implies errorEstimate as noiseThreshold does
+    const bool gvar = get_num(env, s, "guidedVariance", 0) != 0;
+    const double gvar_sigma = get_num(env, s, "guidedSigmaVariance", RT_GUIDED_DEFAULT_SIGMA_VARIANCE);
+    if ((gvar && !(gvar_sigma > 0.0)) || rt_scene_set_guided_variance(box->sc, gvar ? gvar_sigma : 0.0) != RT_OK) {
+        delete job;
+        return throw_err(env, std::string("render: ") + (gvar && !(gvar_sigma > 0.0) ? "guidedSigmaVariance must be > 0" : rt_last_error()));
+    }
+    if (rt_scene_set_error_estimate(box->sc, (gvar || get_num(env, s, "errorEstimate", 0) != 0) ? 1 : 0) != RT_OK ||
         rt_scene_set_noise_threshold(box->sc, get_num(env, s, "noiseThreshold", 0.0), (int32_t)get_num(env, s, "minSamples", 0)) != RT_OK) {
         delete job;
         return throw_err(env, std::string("render: ") + rt_last_error());

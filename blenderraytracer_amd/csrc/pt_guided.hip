@@ -1,11 +1,13 @@
-// pt_guided.hip — the feature buffers (aov_kernel) and the guided filter (guided_level_kernel) for gfx950.
+// pt_guided.hip — the feature buffers (aov_kernel), the guided filter (guided_level_kernel) and its
+// variance-guided form (vguided_level_kernel) for gfx950.
 //
 // A translation unit of its own, built with the common flags only: the trace kernels' units do not see it,
 // so their code generation stays what it was.  The per-pixel bodies are aov_pixel (pt_path.h) and
-// guided_pixel (pt_guided.h), which tests/hostcheck compiles for the CPU.
+// guided_pixel (pt_guided.h) and vguided_pixel (pt_vguided.h), which tests/hostcheck compiles for the CPU.
 #include <algorithm>
 
 #include "pt_guided.h"
+#include "pt_vguided.h"
 #include "kernel_select.h"
 
 namespace rt {
@@ -117,6 +119,33 @@ hipError_t launch_guided_level(const GuidedLevel& L, const double* in, const flo
     if (L.w <= 0 || L.h <= 0) return hipSuccess;
     hipLaunchKernelGGL(guided_level_kernel, dim3((unsigned)((L.w + 31) / 32), (unsigned)((L.h + 7) / 8)), dim3(32, 8), 0,
                        stream, L, in, guides, out);
+    return hipGetLastError();
+}
+
+// ---- the variance-guided form: the same launch shape, colour and variance frames side by side ---------
+// A level reads 48 bytes per tap (colour and variance) beside the 32-byte guide record, and the 3 x 3 variance
+// prefilter is part of the level's kernel: its nine taps are the level-0 taps' cache lines.  Like
+// guided_level_kernel it is bound by the binary64 exponentials, not by the loads, so there is no LDS tile.
+__global__ __launch_bounds__(256) void vguided_level_kernel(const VGuidedLevel L, const double* __restrict__ cin,
+                                                            const double* __restrict__ vin,
+                                                            const float* __restrict__ guides, double* __restrict__ cout,
+                                                            double* __restrict__ vout) {
+    const int x = blockIdx.x * 32 + threadIdx.x, y = blockIdx.y * 8 + threadIdx.y;
+    if (x >= L.w || y >= L.h) return;
+    double oc[3], ov[3];
+    vguided_pixel(L, cin, vin, guides, x, y, oc, ov);
+    const size_t p = 3 * ((size_t)y * L.w + x);
+    cout[p] = oc[0]; cout[p + 1] = oc[1]; cout[p + 2] = oc[2];
+    if (vout) {
+        vout[p] = ov[0]; vout[p + 1] = ov[1]; vout[p + 2] = ov[2];
+    }
+}
+
+hipError_t launch_vguided_level(const VGuidedLevel& L, const double* cin, const double* vin, const float* guides,
+                                double* cout, double* vout, hipStream_t stream) {
+    if (L.w <= 0 || L.h <= 0) return hipSuccess;
+    hipLaunchKernelGGL(vguided_level_kernel, dim3((unsigned)((L.w + 31) / 32), (unsigned)((L.h + 7) / 8)), dim3(32, 8), 0,
+                       stream, L, cin, vin, guides, cout, vout);
     return hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 #include "../../include/rt_hip.h"
 #include "pt_launch.h"
 #include "pt_guided.h"
+#include "pt_vguided.h"
 #include "pt_error.h"
 #include "pool_order.h"
 #include "scene_pack.h"
@@ -422,6 +423,13 @@ struct rt_scene {
     DevBuf<float> guides;
     hipEvent_t g_used = nullptr;
     bool g_used_recorded = false;
+    // the variance-guided form (rt_scene_set_guided_variance, pt_vguided.h): gvar_sigma > 0 is on.  gv_var: the
+    // error estimate's var_mean of the frame; gv_ping / gv_pong: the levels' variance frames, gv_pong the last
+    // level's (rt_guided_filtered_variance: gv_pixels pixels, 0 = none); gv_aux: rt_guided_filter_variance_device's
+    // second scratch frame (it leaves gv_pong alone).  Under the g_used protocol like the colour frames
+    double gvar_sigma = 0.0;
+    DevBuf<double> gv_var, gv_ping, gv_pong, gv_aux;
+    size_t gv_pixels = 0;
     // the error estimate (rt_scene_set_error_estimate, pt_error.h).  err_q: the pixels' second moments of the
     // samples home.sum holds (err_valid), err_groups chunk partials each; err_tile: the frame reduction's tile
     // partials; err_var / err_rel: rt_error_estimate's staging.  err_stats: the figures complete() read last
@@ -570,12 +578,34 @@ hipError_t guided_levels(int w, int h, const rt_guided_params& p, const double* 
     return hipSuccess;
 }
 
+// The levels of the variance-guided form: (color, var) -> ... -> (out, vout) with (tmp, vtmp) in between, by
+// guided_levels' rule.  keep_var false: the last level writes no variance (vout is then only a scratch frame,
+// unused with one level)
+hipError_t vguided_levels(int w, int h, const rt_guided_params& p, double sigma_variance, const double* color,
+                          const double* var, const float* guides, double* out, double* vout, double* tmp, double* vtmp,
+                          bool keep_var, hipStream_t st) {
+    const double *src = color, *vsrc = var;
+    for (int l = 0; l < p.levels; ++l) {
+        const bool to_out = (p.levels - 1 - l) % 2 == 0;
+        double* dst = to_out ? out : tmp;
+        double* vdst = l == p.levels - 1 && !keep_var ? nullptr : to_out ? vout : vtmp;
+        if (const hipError_t e = launch_vguided_level(vguided_level(w, h, p, sigma_variance, l), src, vsrc, guides, dst, vdst, st))
+            return e;
+        src = dst;
+        vsrc = vdst;
+    }
+    return hipSuccess;
+}
+
 // mean, toneMap, gammaCorrect (+ PostProcessor.denoise), RGBA8 on `st` (ray-tracer.js:208-276).
 // thresholds: an RGBA8-only epilogue through the gamma table (preview_kernel: the same bytes, 29 VGPRs
 // instead of finalize_kernel's 80)
 // While the guided filter is set (rt_scene_set_guided; full frames only, check_guided): the mean sum / samples,
 // the frame's feature buffers, the filter, then the same kernels on the filtered mean with samples = 1 (x / 1
 // is x: `mean` is the filtered mean).  `sum` is only read.
+// With the variance form on (rt_scene_set_guided_variance; render_impl has checked that the render commits an
+// estimate of at least 2 groups over the scene's own sums): var_mean of the committed samples and groups into
+// gv_var, then the variance levels instead of the plain ones; gv_pong keeps the propagated variance.
 hipError_t epilogue(rt_scene* sc, const rt_settings* s, int cw, int ch, const double* sum, double* mean, float* post,
                     uint8_t* rgba, hipStream_t st, bool thresholds = false) {
     FinalizeParams fp{cw * ch, s->samples, s->tone_map, s->exposure, s->gamma};
@@ -586,10 +616,32 @@ hipError_t epilogue(rt_scene* sc, const rt_settings* s, int cw, int ch, const do
         if (e == hipSuccess) e = guided_ensure(sc, sc->g_ping, 3 * n);
         if (e == hipSuccess) e = guided_ensure(sc, sc->g_pong, 3 * n);
         if (e == hipSuccess) e = guided_ensure(sc, sc->guides, 8 * n);
+        const bool variance = sc->gvar_sigma > 0.0;
+        if (variance) {
+            if (sum != sc->home.sum.p || !sc->err_on || !sc->err_valid || sc->err_groups < 2 || sc->err_samples <= 0)
+                return hipErrorInvalidValue;
+            sc->gv_pixels = 0;
+            if (e == hipSuccess) e = guided_ensure(sc, sc->gv_var, 3 * n);
+            if (e == hipSuccess) e = guided_ensure(sc, sc->gv_ping, 3 * n);
+            if (e == hipSuccess) e = guided_ensure(sc, sc->gv_pong, 3 * n);
+        }
         if (e == hipSuccess) e = guided_scratch_begin(sc, st);
         if (e == hipSuccess) e = launch_mean(sum, s->samples, sc->g_mean.p, 3 * n, st);
+        if (e == hipSuccess && variance) {
+            ImageParams im{};
+            im.cw = cw;
+            im.ch = ch;
+            e = launch_error_estimate(im, sum, sc->err_q.p, sc->err_groups, sc->err_samples, sc->gv_var.p, nullptr, nullptr,
+                                      nullptr, st);
+        }
         if (e == hipSuccess) e = aovs_on(sc, s, cw, ch, sc->guides.p, nullptr, nullptr, st);
-        if (e == hipSuccess) e = guided_levels(cw, ch, sc->guided, sc->g_mean.p, sc->guides.p, sc->g_pong.p, sc->g_ping.p, st);
+        if (e == hipSuccess && !variance)
+            e = guided_levels(cw, ch, sc->guided, sc->g_mean.p, sc->guides.p, sc->g_pong.p, sc->g_ping.p, st);
+        if (e == hipSuccess && variance) {
+            e = vguided_levels(cw, ch, sc->guided, sc->gvar_sigma, sc->g_mean.p, sc->gv_var.p, sc->guides.p, sc->g_pong.p,
+                               sc->gv_pong.p, sc->g_ping.p, sc->gv_ping.p, true, st);
+            if (e == hipSuccess) sc->gv_pixels = n;
+        }
         if (e != hipSuccess) return e;
         sum = sc->g_pong.p;
         fp.samples = 1;
@@ -616,6 +668,15 @@ hipError_t epilogue(rt_scene* sc, const rt_settings* s, int cw, int ch, const do
 int check_guided(const rt_scene* sc, const rt_settings* s, int cw, int ch) {
     if (sc->guided_on && (cw != s->width || ch != s->height))
         return fail(RT_ERR_INVALID, "the guided filter needs the full frame (its taps reach across the image)");
+    return RT_OK;
+}
+
+// the variance form's needs that do not depend on the batches: the guided filter set (check_guided: the full
+// frame) and the error estimate on
+int check_guided_variance(const rt_scene* sc) {
+    if (!(sc->gvar_sigma > 0.0)) return RT_OK;
+    if (!sc->guided_on) return fail(RT_ERR_INVALID, "the variance-guided form needs the guided filter set (rt_scene_set_guided)");
+    if (!sc->err_on) return fail(RT_ERR_INVALID, "the variance-guided form needs the error estimate on (rt_scene_set_error_estimate)");
     return RT_OK;
 }
 
@@ -1049,6 +1110,7 @@ void rt_scene_destroy(rt_scene* sc) {
     (void)hipSetDevice(sc->home.device);
     sc->mean.release(); sc->post.release(); sc->post_raw.release();
     sc->g_mean.release(); sc->g_ping.release(); sc->g_pong.release(); sc->guides.release();
+    sc->gv_var.release(); sc->gv_ping.release(); sc->gv_pong.release(); sc->gv_aux.release();
     sc->err_q.release(); sc->err_tile.release(); sc->err_var.release(); sc->err_rel.release();
     if (sc->g_used) (void)hipEventDestroy(sc->g_used);
     for (MergeSlot& m : sc->merge) m.release();
@@ -1166,6 +1228,9 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
     const rt_settings* s = &s_local;
     if (!rc) rc = check_accel(sc, s);
     if (!rc) rc = check_guided(sc, s, cw, ch);
+    if (!rc) rc = check_guided_variance(sc);
+    if (!rc && sc->gvar_sigma > 0.0 && sums_in)
+        rc = fail(RT_ERR_INVALID, "the variance-guided form needs the error estimate: a resume from host sums leaves none");
     if (rc) return rc;
     // the error estimate reads the sample pool's chunk partials: renders without them are refused while it is on
     if (sc->err_on) {
@@ -1327,6 +1392,14 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         sc->err_key = ckpt_key(s, cw, ch);
         if (nb > 0) sc->err_stats.chunk_samples = err_chunk;
         else err_chunk = sc->err_stats.chunk_samples;
+    }
+    // the variance-guided epilogue reads var_mean: refused here, before anything is traced, unless the finished
+    // render holds an estimate of at least 2 groups (a noise-threshold stop never comes before 2 groups)
+    if (sc->gvar_sigma > 0.0) {
+        const int groups = !err_active ? 0 : nb > 0 ? groups_after[nb - 1] : sc->err_groups;
+        if (groups < 2)
+            return fail(RT_ERR_INVALID, "the variance-guided form needs an estimate of at least 2 groups: this render would "
+                        "commit %d (more batches, or a resident resume of a render with an estimate)", groups);
     }
     bool fused_launched = false;
     for (int k = 0; k < nsh; ++k) {
@@ -2075,6 +2148,9 @@ int rt_finalize_device(rt_scene* sc, const rt_settings* s, const double* d_sum, 
     int cw, ch;
     int rc = check_settings(s, &cw, &ch);
     if (!rc) rc = check_guided(sc, s, cw, ch);
+    if (!rc && sc->gvar_sigma > 0.0)
+        rc = fail(RT_ERR_INVALID, "rt_finalize_device has no error estimate (rt_trace_device produces none): switch the "
+                  "variance-guided form off");
     if (rc) return rc;
     HIP_TRY(hipSetDevice(sc->home.device));
     HIP_TRY(epilogue(sc, s, cw, ch, d_sum, d_mean, d_post, d_rgba8, (hipStream_t)hip_stream, true));
@@ -2234,6 +2310,61 @@ int rt_guided_filter_device(rt_scene* sc, int32_t width, int32_t height, const r
     HIP_TRY(guided_scratch_begin(sc, st));
     HIP_TRY(guided_levels(width, height, *p, d_color, d_guides, d_out, sc->g_ping.p, st));
     HIP_TRY(guided_scratch_end(sc, st));
+    return RT_OK;
+}
+
+int rt_scene_set_guided_variance(rt_scene* sc, double sigma_variance) {
+    // the parameter first: a bad one is RT_ERR_INVALID with or without a device (or a scene)
+    if (!(sigma_variance >= 0.0)) return fail(RT_ERR_INVALID, "sigma_variance %g: 0 (off) or > 0", sigma_variance);
+    if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
+    sc->gvar_sigma = sigma_variance > 0.0 ? sigma_variance : 0.0;
+    return RT_OK;
+}
+
+int rt_guided_filter_variance_device(rt_scene* sc, int32_t width, int32_t height, const rt_guided_params* p,
+                                     double sigma_variance, const double* d_color, const double* d_var, const float* d_guides,
+                                     double* d_out, double* d_var_out, void* hip_stream) {
+    if (p && !guided_params_ok(p))
+        return fail(RT_ERR_INVALID, "guided parameters: levels %d (1 .. %d), sigmas (%g, %g, %g, %g) each > 0", p->levels,
+                    RT_GUIDED_MAX_LEVELS, p->sigma_color, p->sigma_albedo, p->sigma_normal, p->sigma_depth);
+    if (!vguided_sigma_ok(sigma_variance)) return fail(RT_ERR_INVALID, "sigma_variance %g: must be > 0", sigma_variance);
+    if (!sc || !p || !d_color || !d_var || !d_guides || !d_out) return fail(RT_ERR_INVALID, "NULL argument");
+    if (width <= 0 || height <= 0) return fail(RT_ERR_INVALID, "image %dx%d", width, height);
+    if (((uintptr_t)d_guides & 15) != 0) return fail(RT_ERR_INVALID, "d_guides is not 16-byte aligned");
+    const size_t n = (size_t)width * height;
+    struct Span { uintptr_t a, b; };
+    const auto span = [](const void* q, size_t bytes) { return Span{(uintptr_t)q, (uintptr_t)q + bytes}; };
+    const auto overlap = [](Span x, Span y) { return x.a < y.b && y.a < x.b; };
+    const Span ins[3] = {span(d_color, 24 * n), span(d_var, 24 * n), span(d_guides, 32 * n)};
+    const Span so = span(d_out, 24 * n), sv = span(d_var_out, d_var_out ? 24 * n : 0);
+    for (const Span& in : ins)
+        if (overlap(so, in) || (d_var_out && overlap(sv, in)))
+            return fail(RT_ERR_INVALID, "an output overlaps an input (the filter never runs in place)");
+    if (d_var_out && overlap(so, sv)) return fail(RT_ERR_INVALID, "d_out and d_var_out overlap");
+    const hipStream_t st = (hipStream_t)hip_stream;
+    HIP_TRY(hipSetDevice(sc->home.device));
+    if (p->levels > 1) {
+        HIP_TRY(guided_ensure(sc, sc->g_ping, 3 * n));
+        HIP_TRY(guided_ensure(sc, sc->gv_ping, 3 * n));
+        if (!d_var_out) HIP_TRY(guided_ensure(sc, sc->gv_aux, 3 * n));
+    }
+    HIP_TRY(guided_scratch_begin(sc, st));
+    HIP_TRY(vguided_levels(width, height, *p, sigma_variance, d_color, d_var, d_guides, d_out,
+                           d_var_out ? d_var_out : sc->gv_aux.p, sc->g_ping.p, sc->gv_ping.p, d_var_out != nullptr, st));
+    HIP_TRY(guided_scratch_end(sc, st));
+    return RT_OK;
+}
+
+int rt_guided_filtered_variance(rt_scene* sc, double* var) {
+    if (!sc || !var) return fail(RT_ERR_INVALID, "NULL argument");
+    if (sc->gv_pixels == 0 || !sc->gv_pong.p)
+        return fail(RT_ERR_INVALID, "no filtered variance (no variance-guided epilogue has run on this scene)");
+    HIP_TRY(hipSetDevice(sc->home.device));
+    const hipStream_t st = sc->home.stream;
+    HIP_TRY(guided_scratch_begin(sc, st));
+    HIP_TRY(hipMemcpyAsync(var, sc->gv_pong.p, 3 * sc->gv_pixels * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(guided_scratch_end(sc, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return RT_OK;
 }
 

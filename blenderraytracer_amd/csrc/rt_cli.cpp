@@ -6,7 +6,7 @@
 //                 [--accel auto|bvh|brute] [--frames K] [--warmup W] [--batch B] [--device N]
 //                 [--out image.ppm|image.pam] [--lights] [--nee]
 //                 [--guided] [--guided-levels N] [--guided-sigma C,A,N,Z] [--aovs PREFIX]
-//                 [--noise T] [--min-spp N]
+//                 [--guided-variance [S]] [--noise T] [--min-spp N]
 //
 // --noise T: stop at the first progress batch after which the frame's estimated error (rt_error_stats.frame_error)
 // is at or under T; --min-spp N: not before N samples.  Either implies the error estimate
@@ -14,6 +14,9 @@
 // the JSON line then carries samples_done, frame_error and converged
 // --guided: the edge-aware guided filter over the linear mean (rt_scene_set_guided; --guided-levels and
 // --guided-sigma colour,albedo,normal,depth override the defaults and imply it)
+// --guided-variance [S]: the filter's variance-guided form (rt_scene_set_guided_variance) with sigma_variance S
+// (default RT_GUIDED_DEFAULT_SIGMA_VARIANCE); implies --guided and the error estimate, and without --batch about 4
+// progress batches (the form needs at least 2 chunk partials per pixel)
 // --aovs PREFIX: the feature buffers of the primary hit (rt_aovs) as PREFIX.albedo.pfm, PREFIX.normal.pfm (colour
 // PFM) and PREFIX.depth.pfm (greyscale PFM), little-endian binary32, rows bottom-up as PFM has them
 // --nee: sample the scene's emissive spheres and triangles with MIS (rt_scene_set_emitter_sampling; off by default)
@@ -81,7 +84,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "usage: rt_render_cli scene.json [--width W --height H --spp S --depth D --seed N --aa MODE "
                         "--tone MAP --exposure E --gamma G --denoise STRENGTH --precision f64|f32 --accel auto|bvh|brute "
                         "--frames K --warmup W --batch B --device N --out FILE --lights --nee --guided --guided-levels N "
-                        "--guided-sigma C,A,N,Z --aovs PREFIX --noise T --min-spp N]\n");
+                        "--guided-sigma C,A,N,Z --guided-variance [S] --aovs PREFIX --noise T --min-spp N]\n");
         return argc < 2 ? 2 : 0;
     }
     const char* scene_path = argv[1];
@@ -91,7 +94,8 @@ int main(int argc, char** argv) {
     bool estimate = false;
     uint32_t seed = 1;
     std::string aa = "supersampling", tone = "reinhard", precision = "f64", accel = "auto", out, aovs;
-    bool lights = false, guided = false, nee = false;
+    bool lights = false, guided = false, nee = false, gvar = false;
+    double gvar_sigma = RT_GUIDED_DEFAULT_SIGMA_VARIANCE;
     rt_guided_params gp{RT_GUIDED_DEFAULT_LEVELS, 0, RT_GUIDED_DEFAULT_SIGMA_COLOR, RT_GUIDED_DEFAULT_SIGMA_ALBEDO,
                         RT_GUIDED_DEFAULT_SIGMA_NORMAL, RT_GUIDED_DEFAULT_SIGMA_DEPTH};
     for (int i = 2; i < argc; ++i) {
@@ -99,6 +103,14 @@ int main(int argc, char** argv) {
         if (a == "--lights") { lights = true; continue; }
         if (a == "--nee") { nee = true; continue; }
         if (a == "--guided") { guided = true; continue; }
+        if (a == "--guided-variance") {                     // the value is optional
+            gvar = guided = true;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) {
+                gvar_sigma = atof(argv[++i]);
+                if (!(gvar_sigma > 0.0)) die("--guided-variance takes a sigma > 0: ", argv[i]);
+            }
+            continue;
+        }
         if (i + 1 >= argc) die("missing value for ", a.c_str());
         const char* v = argv[++i];
         if (a == "--width") width = atoi(v);
@@ -162,6 +174,13 @@ int main(int argc, char** argv) {
         if (batch <= 0 || (s.samples + batch - 1) / batch < 16) s.batch_samples = -16;
         check(rt_scene_set_error_estimate(scene, 1), "--noise");
         check(rt_scene_set_noise_threshold(scene, noise, min_spp), "--noise");
+    }
+    if (gvar) {
+        if (!estimate) {
+            if (batch <= 0) s.batch_samples = -4;
+            check(rt_scene_set_error_estimate(scene, 1), "--guided-variance");
+        }
+        check(rt_scene_set_guided_variance(scene, gvar_sigma), "--guided-variance");
     }
     if (denoise > 0) {                                       // post-processor.js:55 weights, host exp
         s.denoise = 1;

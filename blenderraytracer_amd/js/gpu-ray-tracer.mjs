@@ -70,7 +70,8 @@ export function settingsOf(rt, opts = {}) {
         // else the options (installGpuRender on a reference RayTracer); unset parameters take the library's defaults
         ...guidedOf(rt, opts),
         // the per-pixel error estimate (opt-in) and the noise-threshold stop, which implies it (INTEGRATION.md §11)
-        errorEstimate: (opts.errorEstimate || opts.noiseThreshold > 0 || opts.minSamples > 0) ? 1 : 0,
+        // (the variance-guided form of the filter reads the estimate, so it implies it too: INTEGRATION.md §12)
+        errorEstimate: (opts.errorEstimate || opts.noiseThreshold > 0 || opts.minSamples > 0 || guidedVarianceOf(rt, opts)) ? 1 : 0,
         noiseThreshold: opts.noiseThreshold > 0 ? opts.noiseThreshold : 0,
         minSamples: opts.minSamples > 0 ? opts.minSamples : 0,
     };
@@ -94,11 +95,16 @@ export function gpuErrorEstimate(rt) {
     return loadNative().errorEstimate(rt.__gpuScene.scene);
 }
 
+function guidedVarianceOf(rt, opts) {
+    return !!(rt.guidedVariance !== undefined ? rt.guidedVariance : opts.guidedVariance);
+}
+
 function guidedOf(rt, opts) {
     const pick = (member, option) => (rt[member] !== undefined ? rt[member] : opts[option]);
-    const g = { guided: pick('guidedDenoise', 'guidedDenoise') ? 1 : 0 };
+    const g = { guided: pick('guidedDenoise', 'guidedDenoise') ? 1 : 0, guidedVariance: guidedVarianceOf(rt, opts) ? 1 : 0 };
     for (const [member, key] of [['guidedLevels', 'guidedLevels'], ['guidedSigmaColor', 'guidedSigmaColor'],
-        ['guidedSigmaAlbedo', 'guidedSigmaAlbedo'], ['guidedSigmaNormal', 'guidedSigmaNormal'], ['guidedSigmaDepth', 'guidedSigmaDepth']]) {
+        ['guidedSigmaAlbedo', 'guidedSigmaAlbedo'], ['guidedSigmaNormal', 'guidedSigmaNormal'], ['guidedSigmaDepth', 'guidedSigmaDepth'],
+        ['guidedSigmaVariance', 'guidedSigmaVariance']]) {
         const v = pick(member, key);
         if (v !== undefined) g[key] = v;
     }
@@ -238,6 +244,8 @@ function blit(rt, res) {
 //        directLighting: render this.world.lights (the reference's own PointLight / DirectionalLight objects),
 //        keepFloatData: also read back the post-gamma Float32 frame into this.floatData,
 //        errorEstimate: keep the per-pixel error estimate (errorStats(), errorEstimate()),
+//        guidedVariance, guidedSigmaVariance: the guided filter's variance-guided form (needs guidedDenoise and
+//        progress batches that commit at least 2 groups; implies errorEstimate),
 //        noiseThreshold, minSamples: stop at the first progress batch whose frame error is at or under the
 //        threshold, not before minSamples samples (implies errorEstimate; also per render: render(onProgress,
 //        {noiseThreshold, minSamples}) or render({noiseThreshold, minSamples, onProgress}))}
@@ -269,6 +277,7 @@ export class GpuRayTracer {
         this.denoising = false; this.denoiseStrength = 0.5;
         this.directLighting = !!opts.directLighting;                // opt-in: render world.lights
         this.guidedDenoise = !!opts.guidedDenoise;                  // opt-in: the guided filter (INTEGRATION.md)
+        this.guidedVariance = !!opts.guidedVariance;                // opt-in: its variance-guided form (INTEGRATION.md §12)
         this.emitterSampling = !!opts.emitterSampling;              // opt-in: sample emissive geometry with MIS (INTEGRATION.md §10)
         const d = defaultScene(this.width, this.height, permutation(opts.seed || 0));
         this.world = d.world;
@@ -308,7 +317,9 @@ export class GpuRayTracer {
         if (p.emitterSampling !== undefined) this.emitterSampling = !!p.emitterSampling;   // (nor this)
         // the guided filter's keys, read only when present (not reference settings either)
         if (p.guidedDenoise !== undefined) this.guidedDenoise = !!p.guidedDenoise;
-        for (const k of ['guidedLevels', 'guidedSigmaColor', 'guidedSigmaAlbedo', 'guidedSigmaNormal', 'guidedSigmaDepth'])
+        if (p.guidedVariance !== undefined) this.guidedVariance = !!p.guidedVariance;   // implies the error estimate
+        for (const k of ['guidedLevels', 'guidedSigmaColor', 'guidedSigmaAlbedo', 'guidedSigmaNormal', 'guidedSigmaDepth',
+            'guidedSigmaVariance'])
             if (p[k] !== undefined) this[k] = p[k];
     }
 

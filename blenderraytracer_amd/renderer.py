@@ -55,6 +55,7 @@ def settings_struct(width, height, samples, max_bounces, anti_aliasing, tone_map
 # the guided filter's defaults (DESIGN.md §4 "Guided filter": the sweep that chose the sigmas)
 GUIDED_LEVELS = capi.RT_GUIDED_DEFAULT_LEVELS
 GUIDED_SIGMAS = dict(capi.RT_GUIDED_DEFAULT_SIGMAS)
+GUIDED_SIGMA_VARIANCE = capi.RT_GUIDED_DEFAULT_SIGMA_VARIANCE   # "Variance-guided filter": its own sweep
 
 
 class GpuRayTracer:
@@ -77,6 +78,8 @@ class GpuRayTracer:
         self.guided_denoise, self.guided_levels = False, GUIDED_LEVELS
         self.guided_sigma_color, self.guided_sigma_albedo = GUIDED_SIGMAS["color"], GUIDED_SIGMAS["albedo"]
         self.guided_sigma_normal, self.guided_sigma_depth = GUIDED_SIGMAS["normal"], GUIDED_SIGMAS["depth"]
+        # its variance-guided form (opt-in; needs guided_denoise and error_estimate=True)
+        self.guided_variance, self.guided_sigma_variance = False, GUIDED_SIGMA_VARIANCE
         self.world, self.camera = default_scene(self.width, self.height, keyed_permutation(seed))
         self.image_data = np.zeros((self.height, self.width, 4), dtype=np.uint8)
         self.float_data = None
@@ -132,6 +135,10 @@ class GpuRayTracer:
                           ("guidedSigmaNormal", "guided_sigma_normal"), ("guidedSigmaDepth", "guided_sigma_depth")):
             if key in params:
                 setattr(self, attr, float(g(key)))
+        if "guidedVariance" in params:
+            self.guided_variance = bool(truthy(g("guidedVariance")))
+        if "guidedSigmaVariance" in params:
+            self.guided_sigma_variance = float(g("guidedSigmaVariance"))
 
     def update_background(self, type, intensity=1.0):
         self.world.sky_intensity = intensity
@@ -199,6 +206,17 @@ class GpuRayTracer:
     def _apply_guided(self, lib, scene):
         p = self.guided_params()
         capi.check(lib.rt_scene_set_guided(scene, None if p is None else C.byref(p)))
+        # (without guided_denoise or GpuRayTracer(error_estimate=True) the render itself is refused: RT_ERR_INVALID)
+        if self.guided_variance and not float(self.guided_sigma_variance) > 0.0:
+            raise RuntimeError("RT_ERR_INVALID: guidedSigmaVariance must be > 0")
+        capi.check(lib.rt_scene_set_guided_variance(scene, float(self.guided_sigma_variance) if self.guided_variance else 0.0))
+
+    def filtered_variance(self):
+        """The propagated variance (h, w, 3) float64 of the last variance-guided render of the full frame
+        (rt_guided_filtered_variance); RuntimeError (RT_ERR_INVALID) when there is none."""
+        var = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        capi.check(capi.load_library().rt_guided_filtered_variance(self.scene_handle(), var.ctypes.data_as(C.POINTER(C.c_double))))
+        return var
 
     def render_aovs(self, crop=None):
         """The feature buffers of the primary hit (rt_aovs): albedo and normal (h, w, 3), depth (h, w) as float32,

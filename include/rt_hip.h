@@ -524,6 +524,36 @@ int rt_error_estimate(rt_scene* scene, const rt_error_output* out);
  * moments, so the caller orders it before the scene's next render. */
 int rt_error_estimate_device(rt_scene* scene, double* d_var_mean, float* d_rel_error, void* hip_stream);
 
+/* The variance-guided form of the guided filter (DESIGN.md §4 "Variance-guided filter"): an
+ * append-only extension of generation 3.  Off by default; while off, every render runs exactly as before.
+ *
+ * The colour term of a tap is |c_p - c_q|^2 / (sigma_variance^2 (vb_p + 2^-40)) on the raw linear colour, vb_p
+ * being the 3 x 3 binomial mean of the channels' summed variance around p; rt_guided_params.sigma_color is not
+ * read, and no sigma is scaled per level.  Every level also propagates the variance, v' = sum w^2 v / (sum w)^2, so
+ * the stop tightens as the levels smooth.  Always binary64.  A pixel whose colour or variance has a non-finite
+ * channel passes through in both outputs and is never averaged into others; a negative variance reads as 0. */
+#define RT_GUIDED_DEFAULT_SIGMA_VARIANCE 4.0   /* the hosts' default (the sweep of DESIGN.md §4) */
+/* sigma_variance: 0 = off (the default); > 0 (+inf allowed) = on; negative or NaN: RT_ERR_INVALID, validated before
+ * any device is touched.  While on, the guided epilogue of rt_render / rt_render_resume filters the mean with the
+ * variance form, var_mean being the error estimate's of the committed samples and groups; the sums and moments
+ * are only read, so checkpoints and resumes are unchanged.  It needs the guided filter set (and so the full
+ * frame) and the error estimate on, and a render that commits at least 2 groups (rt_error_stats.groups):
+ * rt_render / rt_render_resume return RT_ERR_INVALID before anything is traced otherwise — also for a resume from
+ * host sums, which leaves no estimate.  rt_finalize_device returns RT_ERR_INVALID while it is on
+ * (rt_trace_device never produces an estimate).  Running previews and cancelled renders stay unfiltered. */
+int rt_scene_set_guided_variance(rt_scene* scene, double sigma_variance);
+/* The building block on caller buffers: d_color and d_var (width x height x 3 binary64: the linear mean and the
+ * variance of the mean per channel) filtered along d_guides (16-byte aligned) into d_out and d_var_out (the
+ * propagated variance; may be NULL).  The inputs are not written; an output that overlaps an input or the other
+ * output is RT_ERR_INVALID.  params->sigma_color is not read (it must still be > 0).  The intermediate levels use
+ * scratch frames the scene owns.  Asynchronous on hip_stream. */
+int rt_guided_filter_variance_device(rt_scene* scene, int32_t width, int32_t height, const rt_guided_params* params,
+                                     double sigma_variance, const double* d_color, const double* d_var,
+                                     const float* d_guides, double* d_out, double* d_var_out, void* hip_stream);
+/* The propagated variance v' of the scene's last variance-guided epilogue: n x 3 doubles on the host, n the
+ * pixels of that render.  RT_ERR_INVALID when there is none. */
+int rt_guided_filtered_variance(rt_scene* scene, double* var);
+
 /* Request cancellation of an in-flight rt_render on `scene` (the pool kernels read it between items;
  * see rt_render). */
 int rt_cancel(rt_scene* scene);
