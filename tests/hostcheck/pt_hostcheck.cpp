@@ -302,7 +302,9 @@ extern "C" long long ptc_bvh_check(const rt_scene_desc* d, long long n, unsigned
 // (tests/test_sphere_walks.py compares each with tests/sphere_ref.py): walk 0 World order, 1 the ordered
 // two-child walk, 2 the stackless walk, 3 closest_hit_grid, 4 its LDS-copy form, 5 its lean LDS form with
 // the expanded filter.  t = +inf and idx = -1 on a miss.  Returns -2 when the scene has no grid for 3..5.
-extern "C" int ptc_walk_hits(const rt_scene_desc* d, int walk, const double* rays, long long n, double* t, int* idx) {
+// kind (optional): the hit's kind as rt_closest_hits reports it (-1 on a miss); then idx counts within the kind
+// (tests/test_tri_walks.py compares triangles, boxes and planes with tests/prim_ref.py).
+static int walk_hits(const rt_scene_desc* d, int walk, const double* rays, long long n, double* t, int* kind, int* idx) {
     HostView<double> hv;
     if (!hv.init(d)) return -1;
     const SceneView<double>& v = hv.v;
@@ -327,8 +329,16 @@ extern "C" int ptc_walk_hits(const rt_scene_desc* d, int walk, const double* ray
                                             : closest_hit_grid<double, true, 0, false, true>(v, O, D, w, stk);
         t[k] = c.kind == HIT_NONE ? INFINITY : c.t;
         idx[k] = c.kind == HIT_NONE ? -1 : c.idx;
+        if (kind) kind[k] = c.kind;
     }
     return 0;
+}
+extern "C" int ptc_walk_hits(const rt_scene_desc* d, int walk, const double* rays, long long n, double* t, int* idx) {
+    return walk_hits(d, walk, rays, n, t, nullptr, idx);
+}
+extern "C" int ptc_walk_hits_kind(const rt_scene_desc* d, int walk, const double* rays, long long n, double* t, int* kind,
+                                  int* idx) {
+    return walk_hits(d, walk, rays, n, t, kind, idx);
 }
 
 // The grid's binary32 geometry as the walk reads it (build_grid): out = {lo xyz, cell size xyz, grid_far};

@@ -110,6 +110,24 @@ def walk_hits(packed, walk, rays):
     return t, idx
 
 
+def walk_hits_kind(packed, walk, rays, L=None):
+    """walk_hits with rt_closest_hits' outputs: (t, kind, index within the kind); kind = index = -1 on a miss."""
+    L = L or lib()
+    ip = C.POINTER(C.c_int)
+    L.ptc_walk_hits_kind.argtypes = [C.POINTER(capi.SceneDesc), C.c_int, C.POINTER(C.c_double), C.c_longlong,
+                                     C.POINTER(C.c_double), ip, ip]
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    t = np.full(len(rays), np.nan)
+    kind = np.full(len(rays), -2, dtype=np.int32)
+    idx = np.full(len(rays), -2, dtype=np.int32)
+    rc = L.ptc_walk_hits_kind(C.byref(packed.desc), WALKS.index(walk), rays.ctypes.data_as(C.POINTER(C.c_double)), len(rays),
+                              t.ctypes.data_as(C.POINTER(C.c_double)), kind.ctypes.data_as(ip), idx.ctypes.data_as(ip))
+    if rc == -2:
+        return None
+    assert rc == 0
+    return t, kind, idx
+
+
 def grid_geometry(packed):
     """build_grid's result as the walk reads it: dict(lo, cs (binary32 values), n (cells per axis; zeros: no
     grid), far (grid_far), largest (most records in one cell))."""
