@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pool_plan.h"
 #include "pt_path.h"
 
 namespace rt {
@@ -11,9 +12,6 @@ namespace rt {
 // 4..6 cycles (closest hit, shading, regeneration), 7 / 8 walk iterations per lane / per wave, 9 wave
 // iterations whose active lanes all sit at one inner node, 10 / 11 wave iterations with <= 8 / <= 16 lanes walking
 constexpr int kTotalSlots = 12;
-
-// chunk partial sums of one 8x8 tile: 3 channels x 64 pixels, binary64
-constexpr size_t kPartialBytesPerTile = 3 * 64 * sizeof(double);
 
 struct Counters {
     double* sum;               // n*3 running per-pixel radiance sums (read-modify-write)
@@ -74,10 +72,6 @@ template <class R>
 hipError_t launch_trace(const SceneView<R>& sc, const ImageParams& im, const Counters& c, bool bvh, bool pool,
                         hipStream_t stream, double* err_q = nullptr);
 
-// the sample pool's split of `ns` samples of a cw x ch crop: 8x8 tiles, samples per chunk, chunks and the
-// bytes of all chunk partials of one launch
-struct PoolPlan { int tiles, chunk, chunks; size_t part_bytes; };
-PoolPlan pool_plan(int cw, int ch, int ns, bool tri_bvh, int chunk = 0);
 // the pool kernel writing every chunk (even one) into `part` (>= pool_plan(..).part_bytes), sums untouched:
 // batches may trace concurrently on several streams; launch_reduce then adds part to sum in chunk order
 template <class R>
@@ -116,10 +110,6 @@ hipError_t launch_trace_bands(const SceneView<R>& sc, const ImageParams& im, con
                               double* part, size_t part_bytes, PoolPlan* plan, hipStream_t stream);
 hipError_t launch_reduce_tiles(const ImageParams& im, double* sum, const double* part, int tiles, int chunks,
                                int tile0, int ntiles, hipStream_t stream, const ReduceGate* gate = nullptr);
-
-// doubles of one batch's partials in a fused launch, and the items that complete it
-size_t fused_batch_doubles(int cw, int ch, int batch, bool tri_bvh, int chunk);
-uint32_t fused_batch_items(int cw, int ch, int batch, bool tri_bvh, int chunk);
 
 // World.hit of n rays (n x 6 doubles, device) -> t, kind, index (device): rt_closest_hits
 template <class R>

@@ -715,25 +715,6 @@ bool trace_uses_pool() {
     return v;
 }
 
-// Samples per pool wave: ~2 sqrt(ns) (0.75 sqrt(ns) when the scene has a triangle BVH: its walks
-// vary more in length, so shorter waves pay), for spheres doubled (up to ~4 sqrt(ns), <= 128) while
-// the launch would have > 400k waves, halved (>= 4) until it has >= 64k waves (4x the chip's 16k wave slots).  Short waves shorten
-// the frame's drain tail; long ones shorten each wave's own tail (its last items finish at different
-// times) and write fewer chunk partials (each chunk is 24 B per pixel written and read back once).
-// Measured (RTOW f64 Msamples/s): 1080p x 512 spp c45 / c90 7477 / 7436; x 256 c32 / c45 /
-// c64 7363 / 7386 / 7295; x 128 c24 / c32 / c45 7330 / 7219 / 7156; x 64 c8 / c16 / c32 6720 / 7015 /
-// 6947; 4K x 128 c23 / c45 7331 / 7393; mesh50k 256 spp c12 / c16 / c24 / c32 6786 / 6673 / 6687 /
-// 6391; Cornell 512^2 x 64 spp (4096 tiles) 4.  RT_POOL_CHUNK overrides (A/B runs).
-static int pool_chunk(int ns, int tiles, bool tri_bvh) {
-    static const int v = getenv("RT_POOL_CHUNK") ? std::max(1, env_int("RT_POOL_CHUNK", 1)) : 0;
-    if (v) return v;
-    int c = std::min(128, std::max(4, (int)((tri_bvh ? 0.75 : 2.0) * std::sqrt((double)ns) + 0.5)));
-    const int cmax = tri_bvh ? c : std::min(128, std::max(4, (int)(4.0 * std::sqrt((double)ns) + 0.5)));
-    while (c < cmax && (long long)tiles * ((ns + c - 1) / c) > 400000) c = std::min(cmax, c * 2);
-    while (c > 4 && (long long)tiles * ((ns + c - 1) / c) < 65536) c = std::max(4, c / 2);
-    return c;
-}
-
 #endif  // !RT_ONEWAVE_TU
 
 // dynamic LDS of a trace launch: the ordered walk's per-lane stacks (the scene's deepest leaf entries)
@@ -748,8 +729,6 @@ static size_t pool_lds_bytes(const SceneView<R>& sc) {
         return (size_t)64 * (kParkDoubles * sizeof(double) + kParkInts * 4 + std::min(sc.stack_entries, RT_BVH_STACK) * 4);
     return stack_lds_bytes<ACC>(sc);
 }
-
-static int crop_tiles(int cw, int ch) { return ((cw + 7) / 8) * ((ch + 7) / 8); }
 
 // The one-wave pool kernel (trace_pool_kernel) and the lane-per-pixel kernel (trace_kernel) are
 // compiled in a translation unit of their own, pt_onewave.hip (this file with RT_ONEWAVE_TU), with
@@ -1168,16 +1147,6 @@ template hipError_t launch_trace<double>(const SceneView<double>&, const ImagePa
 template hipError_t launch_trace<float>(const SceneView<float>&, const ImageParams&, const Counters&, bool, bool, hipStream_t,
                                         double*);
 
-PoolPlan pool_plan(int cw, int ch, int ns, bool tri_bvh, int chunk) {
-    PoolPlan p{0, 0, 0, 0};
-    if (cw <= 0 || ch <= 0 || ns <= 0) return p;
-    p.tiles = crop_tiles(cw, ch);
-    p.chunk = chunk > 0 ? chunk : pool_chunk(ns, p.tiles, tri_bvh);
-    p.chunks = (ns + p.chunk - 1) / p.chunk;
-    p.part_bytes = (size_t)p.chunks * p.tiles * kPartialBytesPerTile;
-    return p;
-}
-
 // The pool kernel alone, every chunk (even a single one) into `part`: the sums are not touched, so
 // several such launches (batches) may run at once on different streams; launch_reduce adds them.
 // launch_trace_partials, _batches and _bands prepare the image parameters and the plan; this launches.
@@ -1202,14 +1171,6 @@ template hipError_t launch_trace_partials<double>(const SceneView<double>&, cons
                                                   double*, size_t, hipStream_t);
 template hipError_t launch_trace_partials<float>(const SceneView<float>&, const ImageParams&, const Counters&, bool,
                                                  double*, size_t, hipStream_t);
-
-size_t fused_batch_doubles(int cw, int ch, int batch, bool tri_bvh, int chunk) {
-    return pool_plan(cw, ch, batch, tri_bvh, chunk).part_bytes / sizeof(double);
-}
-uint32_t fused_batch_items(int cw, int ch, int batch, bool tri_bvh, int chunk) {
-    const PoolPlan p = pool_plan(cw, ch, batch, tri_bvh, chunk);
-    return (uint32_t)((size_t)p.tiles * p.chunks);
-}
 
 template <class R>
 hipError_t launch_trace_batches(const SceneView<R>& sc, const ImageParams& im0, const Counters& c, bool bvh, int batch,

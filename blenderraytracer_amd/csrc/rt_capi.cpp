@@ -24,6 +24,7 @@
 #include "pt_vguided.h"
 #include "pt_error.h"
 #include "pool_order.h"
+#include "render_plan.h"
 #include "scene_pack.h"
 
 using namespace rt;
@@ -179,13 +180,6 @@ double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
-// Batches in flight per render (render_impl): kSlots partial slots / trace streams per device; the host
-// queues up to kSlots batches per device beyond the one it waits for (lookahead()), each with its own
-// preview staging and completion event (lookahead() + kSlots of them, so a queued batch never writes a
-// frame the host has not read yet).
-constexpr int kSlots = 3;
-inline int lookahead(int devices) { return kSlots * std::max(1, devices); }
-
 // The render's control words (rt_scene::ctl, mapped coherent host memory, read and written by the host
 // and by the kernels of every device): the cancel word, the sticky stop word and the samples the sums
 // hold (ReduceGate), and one `aborted` word per batch slot of the ring.
@@ -194,7 +188,6 @@ constexpr int kCtlStop = 1, kCtlDone = 2, kCtlAborted = 4;
 constexpr int kCtlCancel = 128;
 // fused batches (render_impl): per batch, the flag its last item raises; two `aborted` words (the gates'
 // stand-in, never written; the skipping waves', never read)
-constexpr int kMaxFused = 64;
 constexpr int kCtlFlag = kCtlCancel + kCancelCopies * kCancelStride;
 constexpr int kCtlFusedAborted = kCtlFlag + kMaxFused;
 // the error estimate (pt_error.h): the sticky `converged` word of the threshold stop, and one ErrorWords per
@@ -432,7 +425,7 @@ struct rt_scene {
     size_t gv_pixels = 0;
     // the error estimate (rt_scene_set_error_estimate, pt_error.h).  err_q: the pixels' second moments of the
     // samples home.sum holds (err_valid), err_groups chunk partials each; err_tile: the frame reduction's tile
-    // partials; err_var / err_rel: rt_error_estimate's staging.  err_stats: the figures complete() read last
+    // partials; err_var / err_rel: rt_error_estimate's staging.  err_stats: the figures complete_batch read last
     bool err_on = false, err_valid = false;
     double err_threshold = 0.0;
     int err_min_samples = 0, err_groups = 0, err_samples = 0;
@@ -726,7 +719,7 @@ hipError_t error_after_reduce(rt_scene* sc, const ErrorBatch& eb, const ImagePar
                                   skip, st);
     if (e != hipSuccess) return e;
     ErrorFrame f{};
-    f.tiles = ((im.cw + 7) / 8) * ((im.ch + 7) / 8);
+    f.tiles = crop_tiles(im.cw, im.ch);
     f.groups = eb.groups;
     f.samples = eb.samples;
     f.min_samples = sc->err_min_samples;
@@ -765,6 +758,43 @@ hipError_t trace_overlapped(rt_scene* sc, DeviceState& ds, const rt_settings* s,
     return e;
 }
 
+// A ReduceGate over the scene's control words: the `aborted` word's index, the samples the sums hold once the
+// batch is committed, and (flag >= 0) the completion flag of a fused launch's batch or band
+ReduceGate reduce_gate(const rt_scene* sc, int aborted_word, int32_t done_value, uint32_t* skip, int flag = -1) {
+    ReduceGate g;
+    g.aborted = sc->ctl_dev + aborted_word;
+    g.stop = sc->ctl_dev + kCtlStop;
+    g.done = reinterpret_cast<int32_t*>(sc->ctl_dev + kCtlDone);
+    g.done_value = done_value;
+    g.skip = skip;
+    if (flag >= 0) g.complete = sc->ctl_dev + kCtlFlag + flag;
+    return g;
+}
+
+// The chunk partials `src` (`bytes`) of a replica's batch into slot j of its staging on the home device
+// (`doubles` large), over the replica's stream `st` once `before` has enqueued on it what produces them and
+// the home stream's last reduce of that slot is done; then `reduce` of the staged partials on the home
+// stream, after which the slot is free again.
+template <class Before, class Reduce>
+int stage_and_reduce(rt_scene* sc, DeviceState& ds, MergeSlot& m, int j, hipStream_t st, const double* src, size_t bytes,
+                     size_t doubles, Before&& before, Reduce&& reduce) {
+    DeviceState& h = sc->home;
+    HIP_TRY(hipSetDevice(h.device));
+    HIP_TRY(m.stage[j].ensure(doubles));
+    if (!m.stage_free[j]) HIP_TRY(hipEventCreateWithFlags(&m.stage_free[j], hipEventDisableTiming));
+    HIP_TRY(hipSetDevice(ds.device));
+    HIP_TRY(before());
+    if (m.stage_used[j]) HIP_TRY(hipStreamWaitEvent(st, m.stage_free[j], 0));
+    HIP_TRY(hipMemcpyPeerAsync(m.stage[j].p, h.device, src, ds.device, bytes, st));
+    HIP_TRY(hipEventRecord(ds.traced[j], st));              // its partials copied out
+    HIP_TRY(hipSetDevice(h.device));
+    HIP_TRY(hipStreamWaitEvent(h.stream, ds.traced[j], 0));
+    HIP_TRY(reduce(m.stage[j].p));
+    HIP_TRY(hipEventRecord(m.stage_free[j], h.stream));
+    m.stage_used[j] = true;
+    return RT_OK;
+}
+
 // One whole batch on a replica (the whole-batch split of render_impl): the pool kernel writes the
 // batch's chunk partials into the replica's slot j on its tstream[j]; the same stream then copies them
 // into the home device's staging slot j (once the home stream's last reduce of that slot is done), and
@@ -776,28 +806,22 @@ int trace_replica(rt_scene* sc, DeviceState& ds, MergeSlot& m, const rt_settings
                   const Counters& c, int j, const ReduceGate* gate, const ErrorBatch* eb = nullptr) {
     if (im.max_depth <= 0 || im.s_end <= im.s_begin) return RT_OK;
     DeviceState& h = sc->home;
-    const int cw = im.cw, ch = im.ch;
-    const size_t bytes = pool_plan(cw, ch, im.s_end - im.s_begin, sc->tri_bvh, im.pool_chunk).part_bytes;
+    const size_t bytes = pool_plan(im.cw, im.ch, im.s_end - im.s_begin, sc->tri_bvh, im.pool_chunk).part_bytes;
     const bool bvh = use_bvh(sc, s);
     DevBuf<double>& part = ds.slot_part(j);
     hipStream_t ts = ds.tstream[j];
-    HIP_TRY(hipSetDevice(h.device));
-    HIP_TRY(m.stage[j].ensure(bytes / sizeof(double)));
-    if (!m.stage_free[j]) HIP_TRY(hipEventCreateWithFlags(&m.stage_free[j], hipEventDisableTiming));
-    HIP_TRY(hipSetDevice(ds.device));
-    HIP_TRY(with_view(ds, s->precision, [&](const auto& v) {
-        return launch_trace_partials(v, im, c, bvh, part.p, part.n * sizeof(double), ts);
-    }));
-    if (m.stage_used[j]) HIP_TRY(hipStreamWaitEvent(ts, m.stage_free[j], 0));
-    HIP_TRY(hipMemcpyPeerAsync(m.stage[j].p, h.device, part.p, ds.device, bytes, ts));
-    HIP_TRY(hipEventRecord(ds.traced[j], ts));              // trace + copy out done
-    HIP_TRY(hipSetDevice(h.device));
-    HIP_TRY(hipStreamWaitEvent(h.stream, ds.traced[j], 0));
-    HIP_TRY(launch_reduce(im, h.sum.p, m.stage[j].p, sc->tri_bvh, h.stream, gate));
-    if (eb) HIP_TRY(error_after_reduce(sc, *eb, im, m.stage[j].p, gate, h.stream));
-    HIP_TRY(hipEventRecord(m.stage_free[j], h.stream));
-    m.stage_used[j] = true;
-    return RT_OK;
+    return stage_and_reduce(
+        sc, ds, m, j, ts, part.p, bytes, bytes / sizeof(double),
+        [&] {
+            return with_view(ds, s->precision, [&](const auto& v) {
+                return launch_trace_partials(v, im, c, bvh, part.p, part.n * sizeof(double), ts);
+            });
+        },
+        [&](const double* staged) {
+            hipError_t e = launch_reduce(im, h.sum.p, staged, sc->tri_bvh, h.stream, gate);
+            if (e == hipSuccess && eb) e = error_after_reduce(sc, *eb, im, staged, gate, h.stream);
+            return e;
+        });
 }
 
 // The per-pixel counters (segments, draws) of the replicas of a whole-batch split, added into the home
@@ -873,7 +897,7 @@ hipError_t scratch_idle(DeviceState& ds) {
 int ensure_partials(const rt_scene* sc, DeviceState& ds, int cw, int ch, int samples, bool pool, Counters& c,
                     int chunk = 0, bool single = false) {
     if (!pool || samples <= 0 || cw <= 0 || ch <= 0) return RT_OK;
-    const size_t per_chunk = (size_t)((cw + 7) / 8) * ((ch + 7) / 8) * kPartialBytesPerTile;
+    const size_t per_chunk = (size_t)crop_tiles(cw, ch) * kPartialBytesPerTile;
     size_t want_all = pool_partial_bytes(cw, ch, samples, sc->tri_bvh, chunk);
     if (want_all == 0 && single) want_all = per_chunk;
     if (want_all == 0) return RT_OK;
@@ -980,6 +1004,18 @@ void fill_stats(rt_stats* st, const rt_scene* sc, const rt_settings* s, const un
         st->prim_tests = totals[0] * (uint64_t)sc->num_prims;
         st->algorithmic_bytes = (double)totals[0] * sc->record_bytes + 12.0 * (double)n;
     }
+}
+
+// the statistics of a trace on the home device alone (rt_trace_device, _bands), once its stream has been waited for
+int trace_stats(rt_stats* st, const rt_scene* sc, const rt_settings* s, const DeviceState& ds, const unsigned long long* totals,
+                size_t n, const ImageParams& im, double t_start) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ds.ev[0], ds.ev[1]));
+    st->kernel_ms = ms;
+    st->finalize_ms = 0;
+    fill_stats(st, sc, s, totals, n, im);
+    st->wall_ms = now_ms() - t_start;
+    return RT_OK;
 }
 
 // The device states of a render: shard k of rt_settings.devices (k = 0: the scene's own device when
@@ -1140,13 +1176,6 @@ int rt_cancel(rt_scene* sc) {
 
 namespace {
 
-// Shard k of the sample range [b, e) over n shards (contiguous, sizes differ by at most one).
-void shard_range(int b, int e, int k, int n, int& sb, int& se) {
-    const long long len = e - b;
-    sb = b + (int)(len * k / n);
-    se = b + (int)(len * (k + 1) / n);
-}
-
 // Adds the replicas' sums (and counters) of the batch just traced into the home device's, in shard
 // order, without a host wait: each replica copies its batch sums over xGMI into its own staging slot on
 // the home device from its own stream (the copies of all replicas run at once, one link each) and then
@@ -1187,47 +1216,24 @@ int merge_shards(rt_scene* sc, const std::vector<DeviceState*>& states, size_t n
     return RT_OK;
 }
 
-// rt_render and rt_render_resume: trace samples [first, sample_end) on top of `sums_in` (NULL: zeros;
-// `resident`: the sums the scene's home device already holds, its checkpoint).
-//
-// Batches (rt_settings.batch_samples) are pipelined: batch k+1 is enqueued before the host waits for
-// batch k, so the GPU never idles on the host's progress call.  With the sample pool and more than one
-// batch, consecutive batches also trace on two streams into their own chunk partials (trace_overlapped):
-// the next batch's waves fill the CUs while the previous one drains, and the reduces add the partials in
-// batch order, so the sums are bit-identical to running the batches one after the other (and to a
-// checkpoint + resume at any batch boundary).  A cancel (progress() returning non-zero, rt_cancel) stops
-// the overlapped batches at their next (tile, chunk) item — a wave's item, about a millisecond — and
-// the checkpoint is the batches fully reduced by then (`gated`); without overlapped batches it is
-// observed after a batch, and the batches already queued complete.  Several devices: whole batches
-// round-robin (trace_replica), or every batch split over the devices (merge_shards).
-// rt_settings.batch_samples = -N: about N progress batches whose size is a multiple of the sample pool's
-// chunk for the render (its rule for the whole sample range [sample_begin, samples), as for one device), so
-// that every batch's items are the one-batch render's items.  Batches of ceil(S / N) samples otherwise cut
-// the chunks: mesh50k (chunk 12) in 16 batches of 16 spp takes one 16-sample chunk per batch, +4 % against
-// one batch.  The resolution depends only on the settings and the scene, so a resume sees
-// the same batches.
-int progress_batch(const rt_scene* sc, const rt_settings* s, int cw, int ch, int steps) {
-    const int base = std::max(0, s->sample_begin);
-    const int end = s->sample_end > 0 ? std::min(s->sample_end, s->samples) : s->samples;
-    const int total = std::max(1, end - base);
-    const int target = std::max(1, (total + steps - 1) / steps);
-    if (!use_pool(s)) return target;
-    const int h = pool_plan(cw, ch, total, sc->tri_bvh).chunk;
-    if (h <= 0 || h >= target) return target;
-    return h * std::max(1, (int)std::lround((double)target / (double)h));
-}
+// ---- rt_render and rt_render_resume: render_impl and its stages (the decisions: render_plan.h) ----
 
-int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_progress_fn progress, void* user,
-                rt_stats* stats, const double* sums_in, int first, bool resident = false) {
-    const double t_start = now_ms();
+// Batch kb of a run as its launches see it
+struct Batch {
+    int kb, b, be;                    // samples [b, be)
+    ReduceGate gate;                  // gated runs: the batch's cancel and commit words (gp: &gate, else NULL)
+    const ReduceGate* gp = nullptr;
+    ErrorBatch eb{};                  // the error estimate's launches follow the batch's reduce, under its gate
+    const ErrorBatch* ebp = nullptr;  // (error_after_reduce)
+    bool previewed = false;           // the reduce wrote the running frame too (RT_FUSED_PREVIEW)
+};
+
+// the refusals that need neither the devices nor the plan
+int check_render(const rt_scene* sc, const rt_settings* s, const double* sums_in, int* cw, int* ch) {
     if (!sc) return fail(RT_ERR_INVALID, "scene is NULL");
-    int cw, ch;
-    int rc = check_settings(s_in, &cw, &ch);
-    rt_settings s_local = s_in ? *s_in : rt_settings{};
-    if (!rc && s_local.batch_samples < 0) s_local.batch_samples = progress_batch(sc, s_in, cw, ch, -s_local.batch_samples);
-    const rt_settings* s = &s_local;
+    int rc = check_settings(s, cw, ch);
     if (!rc) rc = check_accel(sc, s);
-    if (!rc) rc = check_guided(sc, s, cw, ch);
+    if (!rc) rc = check_guided(sc, s, *cw, *ch);
     if (!rc) rc = check_guided_variance(sc);
     if (!rc && sc->gvar_sigma > 0.0 && sums_in)
         rc = fail(RT_ERR_INVALID, "the variance-guided form needs the error estimate: a resume from host sums leaves none");
@@ -1240,10 +1246,550 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         if (s->max_depth <= 0) return fail(RT_ERR_INVALID, "the error estimate needs max_depth > 0 (nothing is traced)");
     } else if (sc->err_threshold > 0.0)
         return fail(RT_ERR_INVALID, "a noise threshold needs the error estimate on");
+    return RT_OK;
+}
+
+// One render between its stages: what the stage functions of render_impl share.
+struct RenderRun {
+    rt_scene* const sc;
+    DeviceState& h;                   // the scene's home state
+    rt_settings settings;             // the caller's settings (a threshold stop: `samples` as committed, for the epilogue)
+    const rt_settings* const s = &settings;
+    const rt_output* const out;
+    const double* const sums_in;      // the sums to start from (NULL: zeros, or `resident`: the scene's checkpoint)
+    const bool resident;
+    const int cw, ch;
+    const size_t n = (size_t)cw * ch;
+    const bool want_segs = out && out->segments, want_draws = out && out->draws;
+    bool err_active = false;          // this render starts or continues the scene's error estimate
+    RenderPlan p;
+    ImageParams im{};                 // samples [p.s0, p.s1)
     std::vector<DeviceState*> states;
-    if ((rc = shard_states(sc, s, states))) return rc;
-    // no checkpoint from here until the new sums are consistent (set below, with the samples they hold):
-    // a render that fails in between leaves none, rather than old metadata over overwritten sums
+    std::vector<Counters> cs;         // per state
+    int enqueued = 0;                 // batches [0, enqueued) are queued on the GPU
+    std::vector<unsigned> slots_used; // whole-batch split: the partial slots each device traced into
+    bool fused_launched = false;
+    GammaSlot* thresholds = nullptr;  // the running frames' RGBA8 thresholds for this gamma (preview_kernel)
+    bool stopped = false;             // the noise threshold ended the render early
+
+    RenderRun(rt_scene* sc, const rt_settings& st, const rt_output* out, const double* sums_in, bool resident, int cw, int ch)
+        : sc(sc), h(sc->home), settings(st), out(out), sums_in(sums_in), resident(resident), cw(cw), ch(ch) {}
+    RenderRun(const RenderRun&) = delete;
+
+    // The run's plan (render_plan.h; its fit questions allocate the buffers asked about), the refusals that
+    // depend on it, and the scene's error-estimate state for this render
+    int make_plan(int first) {
+        cs.resize(states.size());
+        slots_used.assign(states.size(), 0);
+        for (DeviceState* ds : states) {
+            HIP_TRY(hipSetDevice(ds->device));
+            HIP_TRY(ds->sum.ensure(3 * n));
+            HIP_TRY(ds->total.ensure(kTotalSlots));
+        }
+        // The error estimate of this render (pt_error.h): rt_render starts it, a resident resume of a render that
+        // has one continues it; a resume from host sums (or from sums without moments) leaves none
+        err_active = sc->err_on && !sums_in && (!resident || (sc->err_valid && sc->err_key == ckpt_key(s, cw, ch)));
+        RenderPlanIn in{};
+        in.cw = cw; in.ch = ch;
+        in.sample_begin = s->sample_begin; in.sample_end = s->sample_end; in.samples = s->samples;
+        in.batch_samples = s->batch_samples; in.max_depth = s->max_depth;
+        in.pool = use_pool(s);
+        in.first = first;
+        in.tri_bvh = sc->tri_bvh;
+        in.shards = (int)states.size();
+        in.home_first = states[0] == &h;
+        in.want_segs = want_segs; in.want_draws = want_draws;
+        in.want_preview = out && out->preview_rgba8;
+        in.err_active = err_active;
+        in.err_groups = resident ? sc->err_groups : 0;
+        in.knobs = render_knobs();
+        hipError_t fit_error = hipSuccess;
+        p = plan_render(in, [&](const FitAsk& a) {
+            DeviceState& ds = *states[a.shard];
+            if (fit_error == hipSuccess) fit_error = hipSetDevice(ds.device);
+            if (fit_error != hipSuccess) return false;
+            return a.kind == FitAsk::Fused ? ensure_fused(ds, a.doubles, a.batches) : ensure_overlap_partials(ds, a.bytes);
+        });
+        HIP_TRY(fit_error);
+        im = image_params(s, cw, ch);
+        im.s_begin = p.s0;
+        if (p.whole() && sc->merge.size() < states.size()) sc->merge.resize(states.size());
+        if (p.gated) {
+            HIP_TRY(hipSetDevice(h.device));
+            HIP_TRY(h.gate_skip.ensure(1));
+        }
+        if (sc->err_on) {
+            if (p.devices == DeviceMode::Split)
+                return fail(RT_ERR_INVALID, "the error estimate needs whole batches per device (this render splits every "
+                            "batch's samples over the devices)");
+            if (sc->err_threshold > 0.0 && p.nb > 1 && !p.gated)
+                return fail(RT_ERR_INVALID, "the noise threshold needs overlapped batches (their commit gates stop the render)");
+            if (!resident) sc->err_groups = sc->err_samples = 0;
+            sc->err_valid = err_active && resident;
+            if (!err_active || !resident) sc->err_stats = rt_error_stats{};
+            ctl_store(sc->ctl, kCtlConverged, 0);
+        }
+        if (err_active) {
+            HIP_TRY(hipSetDevice(h.device));
+            HIP_TRY(sc->err_q.ensure(3 * n));
+            HIP_TRY(sc->err_tile.ensure(3 * (size_t)crop_tiles(cw, ch)));
+            sc->err_key = ckpt_key(s, cw, ch);
+            if (p.nb > 0) sc->err_stats.chunk_samples = p.err_chunk;
+            else p.err_chunk = sc->err_stats.chunk_samples;
+        }
+        // the variance-guided epilogue reads var_mean: refused here, before anything is traced, unless the finished
+        // render holds an estimate of at least 2 groups (a noise-threshold stop never comes before 2 groups)
+        if (sc->gvar_sigma > 0.0 && p.final_groups < 2)
+            return fail(RT_ERR_INVALID, "the variance-guided form needs an estimate of at least 2 groups: this render would "
+                        "commit %d (more batches, or a resident resume of a render with an estimate)", p.final_groups);
+        return RT_OK;
+    }
+
+    // A state's sums and per-pixel counters as the render starts, on its stream: the sums zeroed — on the home
+    // state copied from the caller's sums, or left as they are (the resident checkpoint) — and the counters
+    // zeroed.  c: a state that traces (its work totals zeroed too, and its counters wired into c)
+    int start_sums(DeviceState& ds, Counters* c) {
+        const bool home = &ds == &sc->home;
+        if (resident && home) {
+            // the scene's checkpoint is already in place
+        } else if (sums_in && home)
+            HIP_TRY(hipMemcpyAsync(ds.sum.p, sums_in, 3 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream));
+        else
+            HIP_TRY(hipMemsetAsync(ds.sum.p, 0, 3 * n * sizeof(double), ds.stream));
+        if (c) HIP_TRY(hipMemsetAsync(ds.total.p, 0, kTotalSlots * sizeof(unsigned long long), ds.stream));
+        if (want_segs) {
+            HIP_TRY(ds.segs.ensure(n));
+            HIP_TRY(hipMemsetAsync(ds.segs.p, 0, n * sizeof(uint32_t), ds.stream));
+            if (c) c->segs = ds.segs.p;
+        }
+        if (want_draws) {
+            HIP_TRY(ds.draws.ensure(n));
+            HIP_TRY(hipMemsetAsync(ds.draws.p, 0, n * sizeof(uint32_t), ds.stream));
+            if (c) c->draws = ds.draws.p;
+        }
+        return RT_OK;
+    }
+
+    // Every device's buffers and streams at the start of the batches, the completion events and preview frames
+    // of the ring, and the checkpoint state from which a failing render leaves a consistent checkpoint
+    int prepare_devices() {
+        int rc;
+        for (size_t k = 0; k < states.size(); ++k) {
+            DeviceState& ds = *states[k];
+            HIP_TRY(hipSetDevice(ds.device));
+            Counters& c = cs[k];
+            c = Counters{ds.sum.p, nullptr, nullptr, ds.total.p};
+            c.cancel_dev = ds.cancel_word.p;
+            c.cancel_gen = sc->render_gen;
+            const int ns = p.first_share((int)k);
+            if (!p.overlap() && s->max_depth > 0 &&
+                (rc = ensure_partials(sc, ds, cw, ch, ns, use_pool(s), c, p.batch_chunk((int)k, ns), err_active)))
+                return rc;
+            HIP_TRY(order_scratch(ds, ds.stream));
+            if ((rc = start_sums(ds, &c))) return rc;
+            HIP_TRY(hipEventRecord(ds.ev[0], ds.stream));
+            if (p.overlap()) {                        // the trace streams start after this set-up
+                HIP_TRY(hipEventRecord(ds.setup_ev, ds.stream));
+                for (hipStream_t t : ds.tstream) HIP_TRY(hipStreamWaitEvent(t, ds.setup_ev, 0));
+            }
+        }
+        if (states[0] != &h) {                      // the home device only merges: its buffers start here
+            HIP_TRY(hipSetDevice(h.device));
+            HIP_TRY(h.sum.ensure(3 * n));
+            if ((rc = start_sums(h, nullptr))) return rc;
+        }
+        HIP_TRY(hipSetDevice(h.device));
+        if (err_active && !resident) HIP_TRY(hipMemsetAsync(sc->err_q.p, 0, 3 * n * sizeof(double), h.stream));
+        if ((int)sc->batch_done.size() < p.ring) sc->batch_done.resize(p.ring, nullptr);
+        for (hipEvent_t& e : sc->batch_done)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (p.preview && (sc->preview_host_n < 4 * n || (int)sc->preview_host.size() < p.ring)) {
+            for (uint8_t*& q : sc->preview_host) {
+                if (q) (void)hipHostFree(q);
+                q = nullptr;
+            }
+            sc->preview_host_n = 0;
+            sc->preview_host.assign(p.ring, nullptr);
+            sc->preview_dev.assign(p.ring, nullptr);
+            for (int k = 0; k < p.ring; ++k) {
+                HIP_TRY(hipHostMalloc((void**)&sc->preview_host[k], 4 * n, hipHostMallocMapped));
+                HIP_TRY(hipHostGetDevicePointer((void**)&sc->preview_dev[k], sc->preview_host[k], 0));
+            }
+            sc->preview_host_n = 4 * n;
+        }
+        // the running frames' RGBA8 thresholds for this gamma (exact bytes without a binary64 pow: preview_kernel)
+        if (p.preview) {
+            HIP_TRY(hipSetDevice(h.device));
+            thresholds = gamma_table(sc, s->gamma);
+        }
+        sc->ckpt_pixels = n;
+        sc->ckpt_done = p.s0;
+        sc->ckpt_key = ckpt_key(s, cw, ch);
+        ctl_store(sc->ctl, kCtlStop, 0);
+        ctl_store(sc->ctl, kCtlDone, (uint32_t)p.s0);
+        return RT_OK;
+    }
+
+    // the running frame's epilogue parameters once the sums hold samples [base, done)
+    FinalizeParams frame_params(int done) {
+        return FinalizeParams{(int)n, done - p.base, s->tone_map, s->exposure, s->gamma};
+    }
+
+    // a trace launch's counters with the run's cancel word and the batch's `aborted` word (gated runs)
+    Counters with_cancel(const Batch& bt, Counters c) {
+        if (p.gated) {
+            if (render_knobs().item_cancel) c.cancel = sc->ctl_dev + kCtlCancel;
+            c.aborted = const_cast<uint32_t*>(bt.gate.aborted);
+        }
+        return c;
+    }
+
+    // batch kb's samples, gate and error-estimate figures
+    Batch begin_batch(int kb) {
+        Batch bt{kb, p.batch_begin(kb), p.batch_end(kb)};
+        if (p.gated) {
+            // fused: the batch's flag commits it (a word no kernel writes stands in for `aborted`)
+            const int w = p.fused() ? kCtlFusedAborted : kCtlAborted + kb % p.ring;
+            if (!p.fused()) ctl_store(sc->ctl, w, 0);   // batch kb - ring, the slot's last user, has completed
+            bt.gate = reduce_gate(sc, w, bt.be, sc->home.gate_skip.p, p.fused() ? kb : -1);
+        }
+        bt.eb = ErrorBatch{err_active ? p.groups_after[kb] : 0, bt.be - p.base, kb % p.ring};
+        return bt;
+    }
+
+    // a fused batch's reduce (and the estimate's launches) of the partials `src` on the home stream
+    hipError_t reduce_fused(Batch& bt, const ImageParams& bi, const double* src) {
+        // fused batches with running frames: RT_FUSED_PREVIEW=1 (A/B) the batch's reduce and its frame in one
+        // kernel (reduce_preview_kernel) — measured slower: mesh50k 22 batches with running frames 77.6 vs
+        // 76.1 ms kernel time for the two kernels (config 3: 96.0 vs 95.9), DESIGN.md §4
+        const bool fuse_prev = render_knobs().fused_preview && p.preview && bt.be < p.s1 && thresholds;
+        hipError_t e;
+        if (!fuse_prev) e = launch_reduce(bi, h.sum.p, src, sc->tri_bvh, h.stream, bt.gp);
+        else {
+            e = launch_reduce_preview(bi, h.sum.p, src, sc->tri_bvh, h.stream, bt.gp, frame_params(bt.be),
+                                      thresholds->table(), sc->preview_dev[bt.kb % p.ring]);
+            if (e == hipSuccess) e = gamma_used(thresholds, h.stream);
+            bt.previewed = e == hipSuccess;
+        }
+        if (e == hipSuccess && bt.ebp) e = error_after_reduce(sc, bt.eb, bi, src, bt.gp, h.stream);
+        return e;
+    }
+
+    // Fused batches: every device's one launch of all its batches (device e: batches e, e + nsh, ...; all of
+    // them when nsh = 1), before batch 0's reduce
+    int launch_fused(const Batch& bt) {
+        const int nsh = p.shards;
+        const bool bvh = use_bvh(sc, s);
+        for (int k = 0; k < p.nb; ++k) ctl_store(sc->ctl, kCtlFlag + k, 0);
+        ctl_store(sc->ctl, kCtlFusedAborted, 0);
+        ctl_store(sc->ctl, kCtlFusedAborted + 1, 0);
+        for (int e = 0; e < nsh; ++e) {
+            DeviceState& de = *states[e];
+            HIP_TRY(hipSetDevice(de.device));
+            const int nbe = (p.nb - e + nsh - 1) / nsh;
+            HIP_TRY(hipMemsetAsync(de.fused_count.p, 0, nbe * sizeof(uint32_t), de.tstream[0]));
+            Counters c = with_cancel(bt, cs[e]);
+            c.aborted = sc->ctl_dev + kCtlFusedAborted + 1;   // written by skipping waves, read by no gate
+            c.batch_count = de.fused_count.p;
+            c.batch_flag = sc->ctl_dev + kCtlFlag + e;          // batch k = e + lb * nsh
+            ImageParams fi = im;
+            fi.s_begin = p.s0 + e * p.batch;
+            fi.s_end = p.s1;
+            fi.pool_chunk = p.fchunk;
+            fi.batch_ways = nsh;
+            const size_t fb = de.fused_part.n * sizeof(double);
+            HIP_TRY(with_view(de, s->precision, [&](const auto& v) {
+                return launch_trace_batches(v, fi, c, bvh, p.batch, de.fused_part.p, fb, de.tstream[0]);
+            }));
+            HIP_TRY(hipEventRecord(de.fused_done, de.tstream[0]));
+        }
+        fused_launched = true;
+        return RT_OK;
+    }
+
+    // Fused batches: batch kb's reduce on the home stream once its flag is up — from the device's own fused
+    // partials, or for a replica's batch from their copy on the home device
+    int enqueue_fused(Batch& bt) {
+        const int kb = bt.kb;
+        if (kb == 0)
+            if (int rc = launch_fused(bt)) return rc;
+        const int d = kb % p.shards, lb = kb / p.shards;
+        DeviceState& ds = *states[d];
+        // the host waits for batch kb's flag; without it (a cancel: its items stay untraced) the
+        // consumer stream waits for the device's launch to end, so the gate reads the final words
+        for (;;) {
+            if (ctl_load(sc->ctl, kCtlFlag + kb)) break;
+            if (sc->cancel.load()) {          // (launches registered after rt_cancel's call, too)
+                (void)cancel_pool_launches(sc->ctl_dev + kCtlCancel);
+                break;
+            }
+            const hipError_t q = hipEventQuery(ds.fused_done);
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) {      // a device fault, not a cancel: fail with the HIP error
+                (void)hipGetLastError();
+                return fail(RT_ERR_DEVICE, "fused batch %d: %s", kb, hipGetErrorString(q));
+            }
+            std::this_thread::sleep_for(std::chrono::microseconds(20));
+        }
+        const bool flagged = ctl_load(sc->ctl, kCtlFlag + kb) != 0;
+        ImageParams bi = im;
+        bi.s_begin = bt.b;
+        bi.s_end = bt.be;
+        bi.pool_chunk = p.fchunk;
+        const double* src = ds.fused_part.p + (size_t)lb * p.fdoubles;
+        if (&ds == &h) {
+            HIP_TRY(hipSetDevice(h.device));
+            if (!flagged) HIP_TRY(hipStreamWaitEvent(h.stream, h.fused_done, 0));
+            HIP_TRY(reduce_fused(bt, bi, src));
+            return RT_OK;
+        }
+        const size_t bytes = pool_plan(cw, ch, bt.be - bt.b, sc->tri_bvh, p.fchunk).part_bytes;
+        return stage_and_reduce(
+            sc, ds, sc->merge[d], lb % kSlots, ds.stream, src, bytes, p.fdoubles,
+            [&] { return flagged ? hipSuccess : hipStreamWaitEvent(ds.stream, ds.fused_done, 0); },
+            [&](const double* staged) { return reduce_fused(bt, bi, staged); });
+    }
+
+    // The whole batch on one device, reduced on the home device
+    int enqueue_whole(const Batch& bt) {
+        const RenderPlan::Piece q = p.piece(bt.kb, 0);
+        const int k = q.shard, lj = bt.kb / p.shards, j = lj % kSlots;
+        DeviceState& ds = *states[k];
+        ImageParams bi = im;
+        bi.s_begin = q.begin;
+        bi.s_end = q.end;
+        bi.pool_chunk = q.chunk;
+        HIP_TRY(hipSetDevice(ds.device));
+        slots_used[k] |= 1u << j;
+        if (&ds == &sc->home) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(bt, cs[k]), j, lj >= kSlots, bt.gp, bt.ebp));
+        else return trace_replica(sc, ds, sc->merge[k], s, bi, with_cancel(bt, cs[k]), j, bt.gp, bt.ebp);
+        return RT_OK;
+    }
+
+    // One device, or every batch split over the devices: every shard's launches first (the devices run
+    // together), then the merge of the shards into the home device
+    int enqueue_split(const Batch& bt) {
+        const int kb = bt.kb;
+        for (int k = 0; k < p.pieces(); ++k) {
+            const RenderPlan::Piece q = p.piece(kb, k);
+            DeviceState& ds = *states[k];
+            ImageParams bi = im;
+            bi.s_begin = q.begin;
+            bi.s_end = q.end;
+            bi.pool_chunk = q.chunk;
+            HIP_TRY(hipSetDevice(ds.device));
+            if (p.overlap())
+                HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(bt, cs[k]), kb % kSlots, kb >= kSlots, bt.gp, bt.ebp));
+            else {                                    // (the estimate: one device, launch_trace adds the chunk moments)
+                HIP_TRY(trace(sc, ds, s, bi, cs[k], ds.stream, bt.ebp ? sc->err_q.p : nullptr));
+                if (bt.ebp) HIP_TRY(error_after_reduce(sc, bt.eb, bi, nullptr, nullptr, ds.stream));
+            }
+        }
+        return p.shards > 1 ? merge_shards(sc, states, n, want_segs, want_draws) : RT_OK;
+    }
+
+    // The running frame of the sums' first `done` samples (their mean) into ring slot `slot` on the home stream:
+    // written by the epilogue kernel straight into pinned host memory (over PCIe): a hipMemcpyAsync here is a
+    // blit kernel that waits for wave slots behind the trace waves (measured 7-15 ms per 8-MB frame while
+    // batches overlap)
+    int preview_frame(int done, int slot, bool by_thresholds) {
+        const GammaTable* table = by_thresholds && thresholds ? thresholds->table() : nullptr;
+        HIP_TRY(launch_finalize(frame_params(done), h.sum.p, nullptr, nullptr, sc->preview_dev[slot], h.stream, table));
+        if (table) HIP_TRY(gamma_used(thresholds, h.stream));
+        return RT_OK;
+    }
+
+    // enqueue batch kb (no host wait): every shard's trace, the merge of the shards into the home device,
+    // the preview frame, then batch_done[kb % ring] on the home stream
+    int enqueue_batch(int kb) {
+        Batch bt = begin_batch(kb);
+        bt.gp = p.gated ? &bt.gate : nullptr;
+        bt.ebp = err_active ? &bt.eb : nullptr;
+        int rc = p.fused() ? enqueue_fused(bt) : p.whole() ? enqueue_whole(bt) : enqueue_split(bt);
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(sc->home.device));
+        if (p.preview && bt.be < p.s1 && !bt.previewed && (rc = preview_frame(bt.be, kb % p.ring, true))) return rc;
+        HIP_TRY(hipEventRecord(sc->batch_done[kb % p.ring], sc->home.stream));
+        return RT_OK;
+    }
+
+    // enqueue batches [enqueued, upto).  The host keeps up to p.ahead batches queued beyond the one it waits
+    // for (their ordering on the partial slots is device-side: trace_overlapped), so neither the host's progress
+    // call nor a preview frame ever delays the start of a batch
+    int fill_queue(int upto) {
+        for (; enqueued < std::min(upto, p.nb) && !sc->cancel.load(); ++enqueued)
+            if (int rc = enqueue_batch(enqueued)) return rc;
+        return RT_OK;
+    }
+
+    // the error figures of committed batch kb, from its slot of the control words
+    void commit_error_stats(int kb) {
+        __atomic_thread_fence(__ATOMIC_SEQ_CST);
+        ErrorWords w;
+        memcpy(&w, sc->ctl + kCtlErr + (kb % p.ring) * kErrSlotWords, sizeof w);
+        rt_error_stats& st = sc->err_stats;
+        st.samples = w.samples;
+        st.groups = w.groups;
+        st.chunk_samples = p.err_chunk;
+        st.converged = ctl_load(sc->ctl, kCtlConverged) ? 1 : 0;
+        st.pixels = w.pixels;
+        st.nonfinite_pixels = w.nonfinite;
+        st.frame_error = w.frame_error;
+        st.max_error = w.max_error;
+        sc->err_groups = w.groups;
+        sc->err_samples = w.samples;
+        sc->err_valid = true;
+    }
+
+    // host side of batch kb once batch_done: checkpoint state and the preview frame.  merged: the batch
+    // is in the sums (gated renders: not if a cancel left it unfinished)
+    int complete_batch(int kb, bool& merged) {
+        HIP_TRY(hipEventSynchronize(sc->batch_done[kb % p.ring]));
+        const int be = p.batch_end(kb);
+        merged = !p.gated || (int)ctl_load(sc->ctl, kCtlDone) >= be;
+        if (!merged) return RT_OK;
+        sc->ckpt_done = be;
+        if (err_active) commit_error_stats(kb);
+        // the running frame, unless the next batch has finished too (its frame supersedes this one: the
+        // host does not fall further behind the GPU copying frames nobody will see)
+        if (p.preview && be < p.s1 &&
+            !(kb + 1 < enqueued && hipEventQuery(sc->batch_done[(kb + 1) % p.ring]) == hipSuccess)) {
+            memcpy(out->preview_rgba8, sc->preview_host[kb % p.ring], 4 * n);
+            if (out->preview_samples) *out->preview_samples = be - p.base;
+        }
+        return RT_OK;
+    }
+
+    // A cancel, or the noise threshold's stop (conv), seen after batch kb: what the queued batches still do,
+    // the checkpoint they leave and its frame.  status: RT_OK (the render completed after all, or stopped at
+    // the threshold) or RT_ERR_CANCELLED; the return value: a HIP failure on the way
+    int stop_render(int kb, bool conv, int& status) {
+        if (p.gated) {
+            // the queued batches stop at their next item and are not reduced; once every stream has
+            // drained, the sums hold exactly the batches the gates committed
+            ctl_cancel(sc->ctl, 1);
+            (void)cancel_pool_launches(sc->ctl_dev + kCtlCancel);
+            for (DeviceState* ds : states) ds->sync_all();
+            h.sync_all();
+            sc->ckpt_done = (int)ctl_load(sc->ctl, kCtlDone);
+            if (err_active && sc->ckpt_done > p.s0) commit_error_stats((sc->ckpt_done - p.s0 + p.batch - 1) / p.batch - 1);
+            if (p.preview && sc->ckpt_done > p.base && sc->ckpt_done < p.s1) {   // the checkpoint's frame
+                HIP_TRY(hipSetDevice(h.device));
+                if (int rc = preview_frame(sc->ckpt_done, 0, false)) return rc;
+                HIP_TRY(hipStreamSynchronize(h.stream));
+                memcpy(out->preview_rgba8, sc->preview_host[0], 4 * n);
+                if (out->preview_samples) *out->preview_samples = sc->ckpt_done - p.base;
+            }
+        } else {
+            // the batches in flight finish (and if the last one was among them, the render completed)
+            bool merged = true;
+            for (int k = kb + 1; k < enqueued && status == RT_OK; ++k) status = complete_batch(k, merged);
+        }
+        if (status == RT_OK && sc->ckpt_done < p.s1) {
+            if (conv && !sc->cancel.load() && sc->ckpt_done > p.base) stopped = true;   // RT_OK over the samples done
+            else status = fail(RT_ERR_CANCELLED, "render cancelled after %d samples", sc->ckpt_done);
+        }
+        return RT_OK;
+    }
+
+    // a HIP error inside the pipeline: drain every stream; the checkpoint keeps the last batch whose
+    // merge is known to be complete (complete_batch ran for it), and the scratch is released
+    void drain_after_error() {
+        const std::string err = g_error;
+        for (DeviceState* ds : states) {
+            ds->sync_all();
+            (void)release_scratch(*ds, ds->stream);
+        }
+        sc->home.sync_all();
+        (void)hipGetLastError();
+        g_error = err;
+    }
+
+    // After the batches (all of them, or those a cancel or the threshold left): the counters' merge, the work
+    // totals, then — unless cancelled (status) — the epilogue, the outputs' copies and the statistics
+    int finish_render(int status, rt_stats* stats, double t_start) {
+        if (fused_launched)                         // every launch's last waves (counters, work totals) first
+            for (DeviceState* ds : states) {
+                HIP_TRY(hipSetDevice(ds->device));
+                HIP_TRY(hipStreamWaitEvent(ds->stream, ds->fused_done, 0));
+            }
+        if (p.whole()) {   // every device's accumulation stream after its trace streams; the replicas' counters
+            for (size_t k = 0; k < states.size(); ++k) {
+                DeviceState* ds = states[k];
+                HIP_TRY(hipSetDevice(ds->device));
+                for (int j = 0; j < kSlots; ++j)
+                    if (slots_used[k] & (1u << j)) HIP_TRY(hipStreamWaitEvent(ds->stream, ds->traced[j], 0));
+            }
+            if (int rc = merge_counters(sc, states, n, want_segs, want_draws)) return rc;
+        }
+        unsigned long long totals[kTotalSlots] = {};
+        float kernel_ms = 0;
+        for (DeviceState* ds : states) {
+            unsigned long long t[kTotalSlots] = {};
+            HIP_TRY(hipSetDevice(ds->device));
+            HIP_TRY(hipEventRecord(ds->ev[1], ds->stream));
+            HIP_TRY(hipMemcpyAsync(t, ds->total.p, sizeof t, hipMemcpyDeviceToHost, ds->stream));
+            HIP_TRY(release_scratch(*ds, ds->stream));
+            HIP_TRY(hipStreamSynchronize(ds->stream));
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ds->ev[0], ds->ev[1]));
+            kernel_ms = std::max(kernel_ms, ms);
+            for (int k = 0; k < kTotalSlots; ++k) totals[k] += t[k];
+        }
+        HIP_TRY(hipSetDevice(h.device));
+        HIP_TRY(hipStreamSynchronize(h.stream));          // the merges of the last batch (checkpoint state)
+        if (status != RT_OK) return status;
+        if (stopped) {                              // the epilogue and the statistics over the samples committed
+            settings.samples = sc->ckpt_done - p.base;
+            im.s_end = sc->ckpt_done;
+        }
+        const bool want_mean = out && out->mean, want_post = out && out->post, want_rgba = out && out->rgba8;
+        if (want_mean) HIP_TRY(sc->mean.ensure(3 * n));
+        if (want_post) HIP_TRY(sc->post.ensure(4 * n));
+        if (want_rgba) HIP_TRY(sc->rgba.ensure(4 * n));
+        HIP_TRY(hipEventRecord(sc->ev[0], h.stream));
+        HIP_TRY(epilogue(sc, s, cw, ch, h.sum.p, want_mean ? sc->mean.p : nullptr, want_post ? sc->post.p : nullptr,
+                         want_rgba ? sc->rgba.p : nullptr, h.stream));
+        HIP_TRY(hipEventRecord(sc->ev[1], h.stream));
+        if (want_mean) HIP_TRY(hipMemcpyAsync(out->mean, sc->mean.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h.stream));
+        if (want_post) HIP_TRY(hipMemcpyAsync(out->post, sc->post.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost, h.stream));
+        if (want_rgba) HIP_TRY(hipMemcpyAsync(out->rgba8, sc->rgba.p, 4 * n, hipMemcpyDeviceToHost, h.stream));
+        if (want_segs) HIP_TRY(hipMemcpyAsync(out->segments, h.segs.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h.stream));
+        if (want_draws) HIP_TRY(hipMemcpyAsync(out->draws, h.draws.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h.stream));
+        HIP_TRY(hipStreamSynchronize(h.stream));
+        if (stats) {
+            float fms = 0;
+            HIP_TRY(hipEventElapsedTime(&fms, sc->ev[0], sc->ev[1]));
+            stats->kernel_ms = kernel_ms;
+            stats->finalize_ms = fms;
+            fill_stats(stats, sc, s, totals, n, im);
+            stats->wall_ms = now_ms() - t_start;
+        }
+#if RT_PROFILE
+        const double cyc = (double)(totals[4] + totals[5] + totals[6]);
+        fprintf(stderr, "[rt_profile] wave-max cycles: closest hit %.3f, shading %.3f, regeneration %.3f (%.3e total); "
+                "walk iterations: %.3e per lane, %.3e per wave, lane efficiency %.3f, wave-uniform inner-node share %.3f\n",
+                totals[4] / cyc, totals[5] / cyc, totals[6] / cyc, cyc, (double)totals[7], (double)totals[8],
+                totals[8] ? (double)totals[7] / (64.0 * (double)totals[8]) : 0.0,
+                totals[8] ? (double)totals[9] / (double)totals[8] : 0.0);
+        fprintf(stderr, "[rt_profile] wave walk iterations with <= 8 lanes walking %.3f, <= 16 %.3f\n",
+                totals[8] ? (double)totals[10] / (double)totals[8] : 0.0, totals[8] ? (double)totals[11] / (double)totals[8] : 0.0);
+#endif
+        return RT_OK;
+    }
+};
+
+// rt_render and rt_render_resume: trace samples [first, sample_end) on top of `sums_in` (render_plan.h)
+int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_progress_fn progress, void* user,
+                rt_stats* stats, const double* sums_in, int first, bool resident = false) {
+    const double t_start = now_ms();
+    int cw, ch;
+    int rc = check_render(sc, s_in, sums_in, &cw, &ch);
+    if (rc) return rc;
+    RenderRun r(sc, *s_in, out, sums_in, resident, cw, ch);
+    if ((rc = shard_states(sc, r.s, r.states))) return rc;
+    // no checkpoint from here until the new sums are consistent (set by prepare_devices, with the samples
+    // they hold): a render that fails in between leaves none, rather than old metadata over overwritten sums
     sc->ckpt_pixels = 0;
     sc->cancel.store(0);
     ctl_cancel(sc->ctl, 0);
@@ -1253,458 +1799,17 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
         ~LaunchScope() { forget_pool_launches(word); }
     } launch_scope{sc->ctl_dev + kCtlCancel};
     if (++sc->render_gen == 0) sc->render_gen = 1;   // 0 is the words' initial value
-    for (DeviceState* ds : states) register_cancel_word(sc->ctl_dev + kCtlCancel, ds->device, ds->cancel_word.p, sc->render_gen);
-    const size_t n = (size_t)cw * ch;
-    const bool want_segs = out && out->segments, want_draws = out && out->draws;
-    const bool pool = use_pool(s);
-    ImageParams im = image_params(s, cw, ch);
-    const int base = im.s_begin;                  // the sums hold samples [base, done) of every pixel
-    im.s_begin = std::max(im.s_begin, first);
-    const int s0 = im.s_begin, s1 = std::max(im.s_end, s0);
-    const int nsh = (int)states.size();
-    DeviceState& h = sc->home;
-    static const bool overlap_env = !(getenv("RT_OVERLAP") && getenv("RT_OVERLAP")[0] == '0');   // A/B runs
-    // Several devices with the sample pool: whole batches round-robin (batch k on states[k % nsh],
-    // trace_replica), at least one batch per device — the batch size counts from sample_begin, so a
-    // resume at a batch boundary sees the same batches.  Every batch's pool waves take min(batch, chunk)
-    // samples, chunk being the pool's rule for the whole render (as one device's batches do), so the
-    // sums are bit-identical to the same batches on one device.
-    bool whole = nsh > 1 && pool && s->max_depth > 0 && overlap_env && s1 > s0;
-    // A batch of B samples is split into round(B / h) equal chunks (at least one), h being the pool's
-    // rule for the render's whole share: min(h, B)-sample chunks left a short remainder chunk in every
-    // batch (mesh50k in 16 batches of 16 spp: chunks of 12 + 4, 77.2 ms vs 75.0 ms as one 16-sample
-    // chunk).  B is the batch setting, not the samples left, so a resume sees the same chunks.
-    auto balanced = [](int h, int b) {
-        if (h <= 0 || b <= 0) return h;
-        const int n = std::max(1, (int)std::lround((double)b / (double)h));
-        return (b + n - 1) / n;
-    };
-    int whole_batch = 0, whole_chunk = 0;
-    if (whole) {
-        const int full = s->batch_samples > 0 ? s->batch_samples : std::max(1, s1 - base);
-        whole_batch = std::max(1, std::min(full, (s1 - base + nsh - 1) / nsh));
-        whole_chunk = balanced(pool_plan(cw, ch, std::max(1, s1 - base), sc->tri_bvh).chunk, whole_batch);
-        const int ns = std::min(whole_batch, s1 - s0);
-        const size_t bytes = pool_plan(cw, ch, ns, sc->tri_bvh, std::min(whole_chunk, ns)).part_bytes;
-        for (int k = 0; k < nsh && whole; ++k) {    // every device's partial slots must fit, else split batches
-            HIP_TRY(hipSetDevice(states[k]->device));
-            whole = ensure_overlap_partials(*states[k], bytes);
-        }
-    }
-    const int batch = whole ? whole_batch : s->batch_samples > 0 ? s->batch_samples : std::max(1, s1 - s0);
-    const int nb = s1 > s0 ? (s1 - s0 + batch - 1) / batch : 0;
-    const bool want_preview = out && out->preview_rgba8 && nb > 1;
-    std::vector<Counters> cs(nsh);
-    // Several batches (split mode): every batch's pool waves take min(batch, chunk) samples, chunk being
-    // the pool's rule for the shard's whole share of the render (not for one batch: short chunks lengthen
-    // each wave's drain relative to its work), balanced over the shard's part of a full batch.  The same
-    // batches give the same chunks on a resume (the share is counted from sample_begin), so a resumed
-    // render stays bit-identical — also when the resume has a single batch left (the render as a whole,
-    // from sample_begin, has several: before round 5 that batch took the pool's rule for its own
-    // samples, 1-ulp differences in the resumed sums).
-    std::vector<int> chunk_hint(nsh, whole ? whole_chunk : 0);
-    if (pool && !whole && (nb > 1 || (s->batch_samples > 0 && s->batch_samples < s1 - base)))
-        for (int k = 0; k < nsh; ++k) {
-            int a, b, fa, fb;
-            shard_range(base, s1, k, nsh, a, b);
-            shard_range(0, batch, k, nsh, fa, fb);
-            chunk_hint[k] = balanced(pool_plan(cw, ch, std::max(1, b - a), sc->tri_bvh).chunk, fb - fa);
-        }
-    auto batch_chunk = [&](int k, int ns) { return chunk_hint[k] > 0 ? std::max(1, std::min(chunk_hint[k], ns)) : 0; };
-    // overlapped batches: the pool with several batches (always in whole-batch mode).  Not with per-pixel
-    // counters over a split of every batch: the trace kernels add those directly, and a replica's merge
-    // zeroes them between batches
-    bool overlap = whole || (overlap_env && pool && nb > 1 && s->max_depth > 0 && !(nsh > 1 && (want_segs || want_draws)));
-    for (int k = 0; k < nsh; ++k) {
-        DeviceState& ds = *states[k];
-        HIP_TRY(hipSetDevice(ds.device));
-        HIP_TRY(ds.sum.ensure(3 * n));
-        HIP_TRY(ds.total.ensure(kTotalSlots));
-        if (whole) continue;
-        int b0, b1;
-        shard_range(s0, s0 + std::min(batch, s1 - s0), k, nsh, b0, b1);
-        const int ns = std::max(1, b1 - b0);
-        if (overlap) overlap = ensure_overlap_partials(ds, pool_plan(cw, ch, ns, sc->tri_bvh, batch_chunk(k, ns)).part_bytes);
-    }
-    if (whole && sc->merge.size() < states.size()) sc->merge.resize(states.size());
-    const int ahead = whole ? lookahead(nsh) : kSlots;   // batches queued beyond the one the host waits for
-    const int ring = ahead + kSlots;                      // completion events / preview frames
-    // A cancel inside a batch: the pool kernels read the cancel word before every item, and a batch with
-    // untraced items is never reduced (ReduceGate), nor is any batch after it, so the sums always hold
-    // the batches [0, k) for some k.  For batches reduced on one stream in batch order: one device, or
-    // the whole-batch split.  The split of every batch over devices observes a cancel between batches.
-    static const bool item_cancel = !(getenv("RT_ITEM_CANCEL") && getenv("RT_ITEM_CANCEL")[0] == '0');   // A/B runs
-    static const bool fuse_env = !(getenv("RT_FUSED_BATCHES") && getenv("RT_FUSED_BATCHES")[0] == '0');   // A/B runs
-    // (RT_ITEM_CANCEL=0 with fused batches: the gates run, the kernels poll no cancel word — A/B only)
-    const bool gated = (item_cancel || (fuse_env && nsh == 1)) && overlap && (nsh == 1 || whole);
-    if (gated) {
-        HIP_TRY(hipSetDevice(h.device));
-        HIP_TRY(h.gate_skip.ensure(1));
-    }
-    // Fused batches (one device, overlapped gated batches): every batch in ONE pool launch, its items
-    // batch-major in the pool's queue (launch_trace_batches: the same items, chunks and partials as one
-    // launch per batch), and each batch's reduce enqueued by the host once the batch's last item has
-    // raised its flag — the persistent workgroups never drain between batches (16 batches of config 3
-    // drained for 3.5 % of the trace time).  The reduces (16 VGPRs) and the preview frames (gamma
-    // thresholds, 29 VGPRs) run beside the trace waves, which leave 32 of a SIMD's 512 VGPRs free.
-    // Several devices (the whole-batch split): device d traces its batches k = d, d + N, ... in one launch
-    // (ImageParams::batch_ways), raising batch k's flag; the host then copies that batch's partials to
-    // the home device and reduces them there in batch order — the copies and reduces of trace_replica,
-    // from one launch per device instead of one per batch.
-    int fchunk = 0;
-    size_t fdoubles = 0;
-    bool fused = fuse_env && gated && nb > 1 && nb <= kMaxFused && (whole || (nsh == 1 && states[0] == &h));
-    if (fused) {
-        fchunk = batch_chunk(0, batch);
-        fdoubles = fused_batch_doubles(cw, ch, batch, sc->tri_bvh, fchunk);
-        for (int d = 0; d < nsh && fused; ++d) {
-            HIP_TRY(hipSetDevice(states[d]->device));
-            fused = ensure_fused(*states[d], fdoubles, (nb - d + nsh - 1) / nsh);
-        }
-    }
-    // The error estimate of this render (pt_error.h): rt_render starts it, a resident resume of a render that
-    // has one continues it; a resume from host sums (or from sums without moments) leaves none
-    const bool err_active = sc->err_on && !sums_in && (!resident || (sc->err_valid && sc->err_key == ckpt_key(s, cw, ch)));
-    std::vector<int> groups_after(nb, 0);         // chunk partials per pixel once batch kb is in
-    int err_chunk = 0;
-    if (sc->err_on) {
-        if (nsh > 1 && !whole)
-            return fail(RT_ERR_INVALID, "the error estimate needs whole batches per device (this render splits every "
-                        "batch's samples over the devices)");
-        if (sc->err_threshold > 0.0 && nb > 1 && !gated)
-            return fail(RT_ERR_INVALID, "the noise threshold needs overlapped batches (their commit gates stop the render)");
-        if (!resident) sc->err_groups = sc->err_samples = 0;
-        sc->err_valid = err_active && resident;
-        if (!err_active || !resident) sc->err_stats = rt_error_stats{};
-        ctl_store(sc->ctl, kCtlConverged, 0);
-    }
-    if (err_active) {
-        int g = sc->err_groups;
-        for (int kb = 0; kb < nb; ++kb) {
-            const int b = s0 + kb * batch, ns = std::min(s1, b + batch) - b;
-            const PoolPlan p = pool_plan(cw, ch, ns, sc->tri_bvh, fused ? fchunk : batch_chunk(whole ? kb % nsh : 0, ns));
-            if (kb == 0) err_chunk = p.chunk;
-            groups_after[kb] = g += p.chunks;
-        }
-        HIP_TRY(hipSetDevice(h.device));
-        HIP_TRY(sc->err_q.ensure(3 * n));
-        HIP_TRY(sc->err_tile.ensure(3 * (size_t)((cw + 7) / 8) * ((ch + 7) / 8)));
-        sc->err_key = ckpt_key(s, cw, ch);
-        if (nb > 0) sc->err_stats.chunk_samples = err_chunk;
-        else err_chunk = sc->err_stats.chunk_samples;
-    }
-    // the variance-guided epilogue reads var_mean: refused here, before anything is traced, unless the finished
-    // render holds an estimate of at least 2 groups (a noise-threshold stop never comes before 2 groups)
-    if (sc->gvar_sigma > 0.0) {
-        const int groups = !err_active ? 0 : nb > 0 ? groups_after[nb - 1] : sc->err_groups;
-        if (groups < 2)
-            return fail(RT_ERR_INVALID, "the variance-guided form needs an estimate of at least 2 groups: this render would "
-                        "commit %d (more batches, or a resident resume of a render with an estimate)", groups);
-    }
-    bool fused_launched = false;
-    for (int k = 0; k < nsh; ++k) {
-        DeviceState& ds = *states[k];
-        HIP_TRY(hipSetDevice(ds.device));
-        Counters& c = cs[k];
-        c = Counters{ds.sum.p, nullptr, nullptr, ds.total.p};
-        c.cancel_dev = ds.cancel_word.p;
-        c.cancel_gen = sc->render_gen;
-        int b0, b1;
-        shard_range(s0, s0 + std::min(batch, s1 - s0), k, nsh, b0, b1);
-        const int ns = std::max(1, b1 - b0);
-        if (!overlap && s->max_depth > 0 && (rc = ensure_partials(sc, ds, cw, ch, ns, pool, c, batch_chunk(k, ns), err_active)))
-            return rc;
-        HIP_TRY(order_scratch(ds, ds.stream));
-        if (resident && &ds == &h) {
-            // the scene's checkpoint is already in place
-        } else if (sums_in && &ds == &h)
-            HIP_TRY(hipMemcpyAsync(ds.sum.p, sums_in, 3 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream));
-        else
-            HIP_TRY(hipMemsetAsync(ds.sum.p, 0, 3 * n * sizeof(double), ds.stream));
-        HIP_TRY(hipMemsetAsync(ds.total.p, 0, kTotalSlots * sizeof(unsigned long long), ds.stream));
-        if (want_segs) {
-            HIP_TRY(ds.segs.ensure(n));
-            HIP_TRY(hipMemsetAsync(ds.segs.p, 0, n * sizeof(uint32_t), ds.stream));
-            c.segs = ds.segs.p;
-        }
-        if (want_draws) {
-            HIP_TRY(ds.draws.ensure(n));
-            HIP_TRY(hipMemsetAsync(ds.draws.p, 0, n * sizeof(uint32_t), ds.stream));
-            c.draws = ds.draws.p;
-        }
-        HIP_TRY(hipEventRecord(ds.ev[0], ds.stream));
-        if (overlap) {                            // the trace streams start after this set-up
-            HIP_TRY(hipEventRecord(ds.setup_ev, ds.stream));
-            for (hipStream_t t : ds.tstream) HIP_TRY(hipStreamWaitEvent(t, ds.setup_ev, 0));
-        }
-    }
-    if (states[0] != &h) {                        // the home device only merges: its buffers start here
-        HIP_TRY(hipSetDevice(h.device));
-        HIP_TRY(h.sum.ensure(3 * n));
-        if (resident) {
-            // the scene's checkpoint is already in place
-        } else if (sums_in) HIP_TRY(hipMemcpyAsync(h.sum.p, sums_in, 3 * n * sizeof(double), hipMemcpyHostToDevice, h.stream));
-        else HIP_TRY(hipMemsetAsync(h.sum.p, 0, 3 * n * sizeof(double), h.stream));
-        if (want_segs) {
-            HIP_TRY(h.segs.ensure(n));
-            HIP_TRY(hipMemsetAsync(h.segs.p, 0, n * sizeof(uint32_t), h.stream));
-        }
-        if (want_draws) {
-            HIP_TRY(h.draws.ensure(n));
-            HIP_TRY(hipMemsetAsync(h.draws.p, 0, n * sizeof(uint32_t), h.stream));
-        }
-    }
-    HIP_TRY(hipSetDevice(h.device));
-    if (err_active && !resident) HIP_TRY(hipMemsetAsync(sc->err_q.p, 0, 3 * n * sizeof(double), h.stream));
-    if ((int)sc->batch_done.size() < ring) sc->batch_done.resize(ring, nullptr);
-    for (hipEvent_t& e : sc->batch_done)
-        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (want_preview) {
-        if (sc->preview_host_n < 4 * n || (int)sc->preview_host.size() < ring) {
-            for (uint8_t*& p : sc->preview_host) {
-                if (p) (void)hipHostFree(p);
-                p = nullptr;
-            }
-            sc->preview_host_n = 0;
-            sc->preview_host.assign(ring, nullptr);
-            sc->preview_dev.assign(ring, nullptr);
-            for (int k = 0; k < ring; ++k) {
-                HIP_TRY(hipHostMalloc((void**)&sc->preview_host[k], 4 * n, hipHostMallocMapped));
-                HIP_TRY(hipHostGetDevicePointer((void**)&sc->preview_dev[k], sc->preview_host[k], 0));
-            }
-            sc->preview_host_n = 4 * n;
-        }
-    }
-    // the running frames' RGBA8 thresholds for this gamma (exact bytes without a binary64 pow: preview_kernel)
-    GammaSlot* thresholds = nullptr;
-    if (want_preview) {
-        HIP_TRY(hipSetDevice(h.device));
-        thresholds = gamma_table(sc, s->gamma);
-    }
-    sc->ckpt_pixels = n;
-    sc->ckpt_done = s0;
-    sc->ckpt_key = ckpt_key(s, cw, ch);
-    ctl_store(sc->ctl, kCtlStop, 0);
-    ctl_store(sc->ctl, kCtlDone, (uint32_t)s0);
-
-    int enqueued = 0;                             // batches [0, enqueued) are queued on the GPU
-    std::vector<unsigned> slots_used(nsh, 0);     // whole-batch split: the partial slots each device traced into
-    // enqueue batch kb (no host wait): every shard's trace, the merge of the shards into the home device,
-    // the preview frame, then batch_done[kb % ring] on the home stream
-    auto enqueue = [&](int kb) -> int {
-        const int b = s0 + kb * batch, be = std::min(s1, b + batch);
-        ReduceGate gate;                          // gated: batch kb's cancel and commit words
-        const ReduceGate* gp = nullptr;
-        if (gated) {
-            // fused: the batch's flag commits it (a word no kernel writes stands in for `aborted`)
-            const int w = fused ? kCtlFusedAborted : kCtlAborted + kb % ring;
-            if (!fused) ctl_store(sc->ctl, w, 0);   // batch kb - ring, the slot's last user, has completed
-            gate.aborted = sc->ctl_dev + w;
-            if (fused) gate.complete = sc->ctl_dev + kCtlFlag + kb;
-            gate.stop = sc->ctl_dev + kCtlStop;
-            gate.done = reinterpret_cast<int32_t*>(sc->ctl_dev + kCtlDone);
-            gate.done_value = be;
-            gate.skip = h.gate_skip.p;
-            gp = &gate;
-        }
-        // fused batches with running frames: RT_FUSED_PREVIEW=1 (A/B) the batch's reduce and its frame in one
-        // kernel (reduce_preview_kernel) — measured slower: mesh50k 22 batches with running frames 77.6 vs
-        // 76.1 ms kernel time for the two kernels (config 3: 96.0 vs 95.9), DESIGN.md §4
-        static const bool fused_preview_env = getenv("RT_FUSED_PREVIEW") && getenv("RT_FUSED_PREVIEW")[0] == '1';
-        const bool fuse_prev = fused && fused_preview_env && want_preview && be < s1 && thresholds;
-        bool previewed = false;
-        // the error estimate's launches follow the batch's reduce, under its gate (error_after_reduce)
-        const ErrorBatch eb{err_active ? groups_after[kb] : 0, be - base, kb % ring};
-        const ErrorBatch* ebp = err_active ? &eb : nullptr;
-        auto reduce_batch = [&](const ImageParams& bi, const double* src) -> hipError_t {
-            hipError_t e;
-            if (!fuse_prev) e = launch_reduce(bi, h.sum.p, src, sc->tri_bvh, h.stream, gp);
-            else {
-                FinalizeParams fp{(int)n, be - base, s->tone_map, s->exposure, s->gamma};
-                e = launch_reduce_preview(bi, h.sum.p, src, sc->tri_bvh, h.stream, gp, fp, thresholds->table(),
-                                          sc->preview_dev[kb % ring]);
-                if (e == hipSuccess) e = gamma_used(thresholds, h.stream);
-                previewed = e == hipSuccess;
-            }
-            if (e == hipSuccess && ebp) e = error_after_reduce(sc, eb, bi, src, gp, h.stream);
-            return e;
-        };
-        auto with_cancel = [&](Counters c) {
-            if (gated) {
-                if (item_cancel) c.cancel = sc->ctl_dev + kCtlCancel;
-                c.aborted = const_cast<uint32_t*>(gate.aborted);
-            }
-            return c;
-        };
-        if (fused) {                              // one launch per device, then batch kb's reduce
-            const bool bvh = use_bvh(sc, s);
-            if (kb == 0) {
-                for (int k = 0; k < nb; ++k) ctl_store(sc->ctl, kCtlFlag + k, 0);
-                ctl_store(sc->ctl, kCtlFusedAborted, 0);
-                ctl_store(sc->ctl, kCtlFusedAborted + 1, 0);
-                for (int e = 0; e < nsh; ++e) {   // device e: batches e, e + nsh, ... (all of them when nsh = 1)
-                    DeviceState& de = *states[e];
-                    HIP_TRY(hipSetDevice(de.device));
-                    const int nbe = (nb - e + nsh - 1) / nsh;
-                    HIP_TRY(hipMemsetAsync(de.fused_count.p, 0, nbe * sizeof(uint32_t), de.tstream[0]));
-                    Counters c = with_cancel(cs[e]);
-                    c.aborted = sc->ctl_dev + kCtlFusedAborted + 1;   // written by skipping waves, read by no gate
-                    c.batch_count = de.fused_count.p;
-                    c.batch_flag = sc->ctl_dev + kCtlFlag + e;          // batch k = e + lb * nsh
-                    ImageParams fi = im;
-                    fi.s_begin = s0 + e * batch;
-                    fi.s_end = s1;
-                    fi.pool_chunk = fchunk;
-                    fi.batch_ways = nsh;
-                    const size_t fb = de.fused_part.n * sizeof(double);
-                    HIP_TRY(with_view(de, s->precision, [&](const auto& v) {
-                        return launch_trace_batches(v, fi, c, bvh, batch, de.fused_part.p, fb, de.tstream[0]);
-                    }));
-                    HIP_TRY(hipEventRecord(de.fused_done, de.tstream[0]));
-                }
-                fused_launched = true;
-            }
-            const int d = kb % nsh, lb = kb / nsh;
-            DeviceState& ds = *states[d];
-            // the host waits for batch kb's flag; without it (a cancel: its items stay untraced) the
-            // consumer stream waits for the device's launch to end, so the gate reads the final words
-            for (;;) {
-                if (ctl_load(sc->ctl, kCtlFlag + kb)) break;
-                if (sc->cancel.load()) {          // (launches registered after rt_cancel's call, too)
-                    (void)cancel_pool_launches(sc->ctl_dev + kCtlCancel);
-                    break;
-                }
-                const hipError_t q = hipEventQuery(ds.fused_done);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) {      // a device fault, not a cancel: fail with the HIP error
-                    (void)hipGetLastError();
-                    return fail(RT_ERR_DEVICE, "fused batch %d: %s", kb, hipGetErrorString(q));
-                }
-                std::this_thread::sleep_for(std::chrono::microseconds(20));
-            }
-            const bool flagged = ctl_load(sc->ctl, kCtlFlag + kb) != 0;
-            ImageParams bi = im;
-            bi.s_begin = b;
-            bi.s_end = be;
-            bi.pool_chunk = fchunk;
-            const double* src = ds.fused_part.p + (size_t)lb * fdoubles;
-            if (&ds == &h) {
-                HIP_TRY(hipSetDevice(h.device));
-                if (!flagged) HIP_TRY(hipStreamWaitEvent(h.stream, h.fused_done, 0));
-                HIP_TRY(reduce_batch(bi, src));
-            } else {                              // a replica's batch: its partials to the home device first
-                MergeSlot& m = sc->merge[d];
-                const int j = lb % kSlots;
-                const size_t bytes = pool_plan(cw, ch, be - b, sc->tri_bvh, fchunk).part_bytes;
-                HIP_TRY(hipSetDevice(h.device));
-                HIP_TRY(m.stage[j].ensure(fdoubles));
-                if (!m.stage_free[j]) HIP_TRY(hipEventCreateWithFlags(&m.stage_free[j], hipEventDisableTiming));
-                HIP_TRY(hipSetDevice(ds.device));
-                if (!flagged) HIP_TRY(hipStreamWaitEvent(ds.stream, ds.fused_done, 0));
-                if (m.stage_used[j]) HIP_TRY(hipStreamWaitEvent(ds.stream, m.stage_free[j], 0));
-                HIP_TRY(hipMemcpyPeerAsync(m.stage[j].p, h.device, src, ds.device, bytes, ds.stream));
-                HIP_TRY(hipEventRecord(ds.traced[j], ds.stream));
-                HIP_TRY(hipSetDevice(h.device));
-                HIP_TRY(hipStreamWaitEvent(h.stream, ds.traced[j], 0));
-                HIP_TRY(reduce_batch(bi, m.stage[j].p));
-                HIP_TRY(hipEventRecord(m.stage_free[j], h.stream));
-                m.stage_used[j] = true;
-            }
-        }
-        if (whole && !fused) {                    // the whole batch on one device, reduced on the home device
-            const int k = kb % nsh, lj = kb / nsh, j = lj % kSlots;
-            DeviceState& ds = *states[k];
-            ImageParams bi = im;
-            bi.s_begin = b;
-            bi.s_end = be;
-            bi.pool_chunk = batch_chunk(k, be - b);
-            HIP_TRY(hipSetDevice(ds.device));
-            slots_used[k] |= 1u << j;
-            if (&ds == &h) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(cs[k]), j, lj >= kSlots, gp, ebp));
-            else if (int r = trace_replica(sc, ds, sc->merge[k], s, bi, with_cancel(cs[k]), j, gp, ebp)) return r;
-        }
-        for (int k = 0; k < nsh && !whole && !fused; ++k) { // every shard's launches first: the devices run together
-            DeviceState& ds = *states[k];
-            ImageParams bi = im;
-            shard_range(b, be, k, nsh, bi.s_begin, bi.s_end);
-            bi.pool_chunk = batch_chunk(k, bi.s_end - bi.s_begin);
-            HIP_TRY(hipSetDevice(ds.device));
-            if (overlap) HIP_TRY(trace_overlapped(sc, ds, s, bi, with_cancel(cs[k]), kb % kSlots, kb >= kSlots, gp, ebp));
-            else {                                // (the estimate: one device, launch_trace adds the chunk moments)
-                HIP_TRY(trace(sc, ds, s, bi, cs[k], ds.stream, ebp ? sc->err_q.p : nullptr));
-                if (ebp) HIP_TRY(error_after_reduce(sc, eb, bi, nullptr, nullptr, ds.stream));
-            }
-        }
-        int r;
-        if (nsh > 1 && !whole && (r = merge_shards(sc, states, n, want_segs, want_draws))) return r;
-        HIP_TRY(hipSetDevice(h.device));
-        if (want_preview && be < s1 && !previewed) {   // the running frame: mean over the samples so far
-            // written by the epilogue kernel straight into pinned host memory (over PCIe): a
-            // hipMemcpyAsync here is a blit kernel that waits for wave slots behind the trace waves
-            // (measured 7-15 ms per 8-MB frame while batches overlap)
-            FinalizeParams fp{(int)n, be - base, s->tone_map, s->exposure, s->gamma};
-            HIP_TRY(launch_finalize(fp, h.sum.p, nullptr, nullptr, sc->preview_dev[kb % ring], h.stream,
-                                    thresholds ? thresholds->table() : nullptr));
-            if (thresholds) HIP_TRY(gamma_used(thresholds, h.stream));
-        }
-        HIP_TRY(hipEventRecord(sc->batch_done[kb % ring], h.stream));
-        return RT_OK;
-    };
-    // host side of batch kb once batch_done: checkpoint state and the preview frame.  merged: the batch
-    // is in the sums (gated renders: not if a cancel left it unfinished)
-    // the error figures of committed batch kb, from its slot of the control words
-    auto err_commit = [&](int kb) {
-        __atomic_thread_fence(__ATOMIC_SEQ_CST);
-        ErrorWords w;
-        memcpy(&w, sc->ctl + kCtlErr + (kb % ring) * kErrSlotWords, sizeof w);
-        rt_error_stats& st = sc->err_stats;
-        st.samples = w.samples;
-        st.groups = w.groups;
-        st.chunk_samples = err_chunk;
-        st.converged = ctl_load(sc->ctl, kCtlConverged) ? 1 : 0;
-        st.pixels = w.pixels;
-        st.nonfinite_pixels = w.nonfinite;
-        st.frame_error = w.frame_error;
-        st.max_error = w.max_error;
-        sc->err_groups = w.groups;
-        sc->err_samples = w.samples;
-        sc->err_valid = true;
-    };
-    auto complete = [&](int kb, bool& merged) -> int {
-        HIP_TRY(hipEventSynchronize(sc->batch_done[kb % ring]));
-        const int be = std::min(s1, s0 + (kb + 1) * batch);
-        merged = !gated || (int)ctl_load(sc->ctl, kCtlDone) >= be;
-        if (!merged) return RT_OK;
-        sc->ckpt_done = be;
-        if (err_active) err_commit(kb);
-        // the running frame, unless the next batch has finished too (its frame supersedes this one: the
-        // host does not fall further behind the GPU copying frames nobody will see)
-        if (want_preview && be < s1 &&
-            !(kb + 1 < enqueued && hipEventQuery(sc->batch_done[(kb + 1) % ring]) == hipSuccess)) {
-            memcpy(out->preview_rgba8, sc->preview_host[kb % ring], 4 * n);
-            if (out->preview_samples) *out->preview_samples = be - base;
-        }
-        return RT_OK;
-    };
-    // the host keeps up to kSlots batches queued beyond the one it waits for (their ordering on the
-    // partial slots is device-side: trace_overlapped), so neither the host's progress call nor a preview
-    // frame ever delays the start of a batch
+    for (DeviceState* ds : r.states) register_cancel_word(sc->ctl_dev + kCtlCancel, ds->device, ds->cancel_word.p, sc->render_gen);
+    if ((rc = r.make_plan(first)) || (rc = r.prepare_devices())) return rc;
+    const RenderPlan& p = r.p;
     int status = RT_OK;
-    bool stopped = false;                         // the noise threshold ended the render early
-    auto fill = [&](int upto) -> int {          // enqueue batches [enqueued, upto)
-        for (; enqueued < std::min(upto, nb) && !sc->cancel.load(); ++enqueued) {
-            const int r = enqueue(enqueued);
-            if (r) return r;
-        }
-        return RT_OK;
-    };
-    for (int kb = 0; kb < nb && status == RT_OK; ++kb) {
-        if ((status = fill(kb + (fused ? 0 : ahead) + 1))) break;   // fused: enqueue(kb) waits for batch kb
+    for (int kb = 0; kb < p.nb && status == RT_OK; ++kb) {
+        if ((status = r.fill_queue(kb + (p.fused() ? 0 : p.ahead) + 1))) break;   // fused: enqueue_fused(kb) waits for batch kb
         bool merged = true;
-        if ((status = complete(kb, merged))) break;
+        if ((status = r.complete_batch(kb, merged))) break;
         // the threshold stop (error_frame_kernel set `stop` and `converged` after an earlier batch): the gates
         // skip every later batch, and nobody cancelled
-        const bool conv = err_active && gated && ctl_load(sc->ctl, kCtlConverged) != 0;
+        const bool conv = r.err_active && p.gated && ctl_load(sc->ctl, kCtlConverged) != 0;
         if (!merged && !sc->cancel.load() && !conv) {
             // a gate skipped a batch although nobody cancelled (rt_cancel sets `cancel` before the word the
             // kernels read): an item-count mismatch or a lost flag — an internal failure, not a cancel
@@ -1712,120 +1817,20 @@ int render_impl(rt_scene* sc, const rt_settings* s_in, const rt_output* out, rt_
             break;
         }
         const int be = sc->ckpt_done;
-        if (merged && progress && be < s1 && progress((double)(be - s0) / (double)(s1 - s0), user)) {
+        if (merged && progress && be < p.s1 && progress((double)(be - p.s0) / (double)(p.s1 - p.s0), user)) {
             sc->cancel.store(1);
             ctl_cancel(sc->ctl, 1);
         }
-        if (!merged || sc->cancel.load() || (conv && be < s1)) {
-            if (gated) {
-                // the queued batches stop at their next item and are not reduced; once every stream has
-                // drained, the sums hold exactly the batches the gates committed
-                ctl_cancel(sc->ctl, 1);
-                (void)cancel_pool_launches(sc->ctl_dev + kCtlCancel);
-                for (DeviceState* ds : states) ds->sync_all();
-                h.sync_all();
-                sc->ckpt_done = (int)ctl_load(sc->ctl, kCtlDone);
-                if (err_active && sc->ckpt_done > s0) err_commit((sc->ckpt_done - s0 + batch - 1) / batch - 1);
-                if (want_preview && sc->ckpt_done > base && sc->ckpt_done < s1) {   // the checkpoint's frame
-                    HIP_TRY(hipSetDevice(h.device));
-                    FinalizeParams fp{(int)n, sc->ckpt_done - base, s->tone_map, s->exposure, s->gamma};
-                    HIP_TRY(launch_finalize(fp, h.sum.p, nullptr, nullptr, sc->preview_dev[0], h.stream));
-                    HIP_TRY(hipStreamSynchronize(h.stream));
-                    memcpy(out->preview_rgba8, sc->preview_host[0], 4 * n);
-                    if (out->preview_samples) *out->preview_samples = sc->ckpt_done - base;
-                }
-            } else {
-                // the batches in flight finish (and if the last one was among them, the render completed)
-                for (int k = kb + 1; k < enqueued && status == RT_OK; ++k) status = complete(k, merged);
-            }
-            if (status == RT_OK && sc->ckpt_done < s1) {
-                if (conv && !sc->cancel.load() && sc->ckpt_done > base) stopped = true;   // RT_OK over the samples done
-                else status = fail(RT_ERR_CANCELLED, "render cancelled after %d samples", sc->ckpt_done);
-            }
+        if (!merged || sc->cancel.load() || (conv && be < p.s1)) {
+            if ((rc = r.stop_render(kb, conv, status))) return rc;
             break;
         }
     }
     if (status != RT_OK && status != RT_ERR_CANCELLED) {
-        // a HIP error inside the pipeline: drain every stream; the checkpoint keeps the last batch whose
-        // merge is known to be complete (complete() ran for it), and the scratch is released
-        const std::string err = g_error;
-        for (DeviceState* ds : states) {
-            ds->sync_all();
-            (void)release_scratch(*ds, ds->stream);
-        }
-        h.sync_all();
-        (void)hipGetLastError();
-        g_error = err;
+        r.drain_after_error();
         return status;
     }
-    if (fused_launched)                           // every launch's last waves (counters, work totals) first
-        for (DeviceState* ds : states) {
-            HIP_TRY(hipSetDevice(ds->device));
-            HIP_TRY(hipStreamWaitEvent(ds->stream, ds->fused_done, 0));
-        }
-    if (whole) {   // every device's accumulation stream after its trace streams; the replicas' counters
-        for (int k = 0; k < nsh; ++k) {
-            DeviceState* ds = states[k];
-            HIP_TRY(hipSetDevice(ds->device));
-            for (int j = 0; j < kSlots; ++j)
-                if (slots_used[k] & (1u << j)) HIP_TRY(hipStreamWaitEvent(ds->stream, ds->traced[j], 0));
-        }
-        if ((rc = merge_counters(sc, states, n, want_segs, want_draws))) return rc;
-    }
-    unsigned long long totals[kTotalSlots] = {};
-    float kernel_ms = 0;
-    for (DeviceState* ds : states) {
-        unsigned long long t[kTotalSlots] = {};
-        HIP_TRY(hipSetDevice(ds->device));
-        HIP_TRY(hipEventRecord(ds->ev[1], ds->stream));
-        HIP_TRY(hipMemcpyAsync(t, ds->total.p, sizeof t, hipMemcpyDeviceToHost, ds->stream));
-        HIP_TRY(release_scratch(*ds, ds->stream));
-        HIP_TRY(hipStreamSynchronize(ds->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ds->ev[0], ds->ev[1]));
-        kernel_ms = std::max(kernel_ms, ms);
-        for (int k = 0; k < kTotalSlots; ++k) totals[k] += t[k];
-    }
-    HIP_TRY(hipSetDevice(h.device));
-    HIP_TRY(hipStreamSynchronize(h.stream));          // the merges of the last batch (checkpoint state)
-    if (status != RT_OK) return status;
-    if (stopped) {                                // the epilogue and the statistics over the samples committed
-        s_local.samples = sc->ckpt_done - base;
-        im.s_end = sc->ckpt_done;
-    }
-    const bool want_mean = out && out->mean, want_post = out && out->post, want_rgba = out && out->rgba8;
-    if (want_mean) HIP_TRY(sc->mean.ensure(3 * n));
-    if (want_post) HIP_TRY(sc->post.ensure(4 * n));
-    if (want_rgba) HIP_TRY(sc->rgba.ensure(4 * n));
-    HIP_TRY(hipEventRecord(sc->ev[0], h.stream));
-    HIP_TRY(epilogue(sc, s, cw, ch, h.sum.p, want_mean ? sc->mean.p : nullptr, want_post ? sc->post.p : nullptr,
-                     want_rgba ? sc->rgba.p : nullptr, h.stream));
-    HIP_TRY(hipEventRecord(sc->ev[1], h.stream));
-    if (want_mean) HIP_TRY(hipMemcpyAsync(out->mean, sc->mean.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, h.stream));
-    if (want_post) HIP_TRY(hipMemcpyAsync(out->post, sc->post.p, 4 * n * sizeof(float), hipMemcpyDeviceToHost, h.stream));
-    if (want_rgba) HIP_TRY(hipMemcpyAsync(out->rgba8, sc->rgba.p, 4 * n, hipMemcpyDeviceToHost, h.stream));
-    if (want_segs) HIP_TRY(hipMemcpyAsync(out->segments, h.segs.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h.stream));
-    if (want_draws) HIP_TRY(hipMemcpyAsync(out->draws, h.draws.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, h.stream));
-    HIP_TRY(hipStreamSynchronize(h.stream));
-    if (stats) {
-        float fms = 0;
-        HIP_TRY(hipEventElapsedTime(&fms, sc->ev[0], sc->ev[1]));
-        stats->kernel_ms = kernel_ms;
-        stats->finalize_ms = fms;
-        fill_stats(stats, sc, s, totals, n, im);
-        stats->wall_ms = now_ms() - t_start;
-    }
-#if RT_PROFILE
-    const double cyc = (double)(totals[4] + totals[5] + totals[6]);
-    fprintf(stderr, "[rt_profile] wave-max cycles: closest hit %.3f, shading %.3f, regeneration %.3f (%.3e total); "
-            "walk iterations: %.3e per lane, %.3e per wave, lane efficiency %.3f, wave-uniform inner-node share %.3f\n",
-            totals[4] / cyc, totals[5] / cyc, totals[6] / cyc, cyc, (double)totals[7], (double)totals[8],
-            totals[8] ? (double)totals[7] / (64.0 * (double)totals[8]) : 0.0,
-            totals[8] ? (double)totals[9] / (double)totals[8] : 0.0);
-    fprintf(stderr, "[rt_profile] wave walk iterations with <= 8 lanes walking %.3f, <= 16 %.3f\n",
-            totals[8] ? (double)totals[10] / (double)totals[8] : 0.0, totals[8] ? (double)totals[11] / (double)totals[8] : 0.0);
-#endif
-    return RT_OK;
+    return r.finish_render(status, stats, t_start);
 }
 
 }  // namespace
@@ -1904,14 +1909,7 @@ int rt_trace_device(rt_scene* sc, const rt_settings* s, double* d_sum, void* hip
     HIP_TRY(release_scratch(ds, st));
     if (sync || stats) {
         HIP_TRY(hipStreamSynchronize(st));
-        if (stats) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ds.ev[0], ds.ev[1]));
-            stats->kernel_ms = ms;
-            stats->finalize_ms = 0;
-            fill_stats(stats, sc, s, totals, (size_t)cw * ch, im);
-            stats->wall_ms = now_ms() - t_start;
-        }
+        if (stats) return trace_stats(stats, sc, s, ds, totals, (size_t)cw * ch, im, t_start);
     }
     return RT_OK;
 }
@@ -1999,13 +1997,7 @@ int rt_trace_device_bands(rt_scene* sc, const rt_settings* s, double* d_sum, voi
             std::this_thread::sleep_for(std::chrono::microseconds(20));
         }
         if (status != RT_OK) break;
-        ReduceGate gate;                            // the acquire end of the band's commit (item_done)
-        gate.aborted = sc->ctl_dev + kCtlFusedAborted;
-        gate.stop = sc->ctl_dev + kCtlStop;
-        gate.done = reinterpret_cast<int32_t*>(sc->ctl_dev + kCtlDone);
-        gate.done_value = 0;
-        gate.skip = ds.gate_skip.p;
-        gate.complete = sc->ctl_dev + kCtlFlag + b;
+        const ReduceGate gate = reduce_gate(sc, kCtlFusedAborted, 0, ds.gate_skip.p, b);   // the acquire end of the band's commit (item_done)
         const int r0 = band_row0(im, b), r1 = band_row0(im, b + 1);
         hipError_t e = launch_reduce_tiles(im, d_sum, ds.part.p, used.tiles, used.chunks, r0 * tiles_x,
                                            (r1 - r0) * tiles_x, st, &gate);
@@ -2026,12 +2018,7 @@ int rt_trace_device_bands(rt_scene* sc, const rt_settings* s, double* d_sum, voi
     }
     if (stats) {
         HIP_TRY(hipStreamSynchronize(st));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ds.ev[0], ds.ev[1]));
-        stats->kernel_ms = ms;
-        stats->finalize_ms = 0;
-        fill_stats(stats, sc, s, totals, (size_t)cw * ch, im);
-        stats->wall_ms = now_ms() - t_start;
+        return trace_stats(stats, sc, s, ds, totals, (size_t)cw * ch, im, t_start);
     }
     return RT_OK;
 }

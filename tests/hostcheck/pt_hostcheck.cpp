@@ -8,6 +8,7 @@
 #include "../../blenderraytracer_amd/csrc/scene_pack.h"
 #include "../../blenderraytracer_amd/csrc/pool_order.h"
 #include "../../blenderraytracer_amd/csrc/kernel_select.h"
+#include "../../blenderraytracer_amd/csrc/render_plan.h"
 
 using namespace rt;
 
@@ -509,6 +510,53 @@ extern "C" void ptc_default_knobs(int* out) {
     const SelectKnobs k;
     const int v[] = {k.bvh_walk, k.lean, k.lds_grid, k.lds_nodes, k.lds_tri, k.tri_lds_nodes};
     std::memcpy(out, v, sizeof(v));
+}
+
+// A render's plan (render_plan.h plan_render, TEST TOOL).  in = {cw, ch, sample_begin, sample_end, samples,
+// batch_samples, max_depth, pool, first, tri_bvh, shards, home_first, want_segs, want_draws, want_preview, err_active,
+// err_groups, knobs (bits: overlap, item_cancel, fused_batches, fused_preview), refuse_fused, refuse_slots_shard (-1:
+// none)}: the fit callable says yes except to the fused buffers (refuse_fused) and to that shard's overlap slots.
+// out[0..15] = {base, s0, s1, batch, nb, device mode, queue mode, gated, preview, ahead, ring, fchunk, fdoubles,
+// err_chunk, final_groups, questions asked}, out[16..23] chunk_hint, out[24..31] slot_bytes, out[32..79] the
+// questions in order (kind, shard, bytes or doubles), from out[80] six values per launch of every batch: {begin,
+// end, shard, chunk, chunks, groups_after of its batch}.  Returns the values written, -1 if cap is too small.
+extern "C" long long ptc_render_plan(const int* in, long long* out, long long cap) {
+    RenderPlanIn pi{};
+    pi.cw = in[0]; pi.ch = in[1];
+    pi.sample_begin = in[2]; pi.sample_end = in[3]; pi.samples = in[4]; pi.batch_samples = in[5]; pi.max_depth = in[6];
+    pi.pool = in[7] != 0; pi.first = in[8]; pi.tri_bvh = in[9] != 0; pi.shards = in[10]; pi.home_first = in[11] != 0;
+    pi.want_segs = in[12] != 0; pi.want_draws = in[13] != 0; pi.want_preview = in[14] != 0;
+    pi.err_active = in[15] != 0; pi.err_groups = in[16];
+    pi.knobs = RenderKnobs{(in[17] & 1) != 0, (in[17] & 2) != 0, (in[17] & 4) != 0, (in[17] & 8) != 0};
+    if (pi.shards < 1 || pi.shards > 8 || cap < 80) return -1;
+    std::memset(out, 0, 80 * sizeof(long long));
+    int asks = 0;
+    const RenderPlan p = plan_render(pi, [&](const FitAsk& a) {
+        const bool fused = a.kind == FitAsk::Fused;
+        if (asks < 16) {
+            const long long v[] = {fused, a.shard, (long long)(fused ? a.doubles : a.bytes)};
+            std::memcpy(out + 32 + 3 * asks, v, sizeof v);
+        }
+        ++asks;
+        return fused ? in[18] == 0 : a.shard != in[19];
+    });
+    const long long head[] = {p.base, p.s0, p.s1, p.batch, p.nb, (int)p.devices, (int)p.queue, p.gated, p.preview, p.ahead,
+                              p.ring, p.fchunk, (long long)p.fdoubles, p.err_chunk, p.final_groups, asks};
+    std::memcpy(out, head, sizeof head);
+    for (int k = 0; k < pi.shards; ++k) {
+        out[16 + k] = p.chunk_hint[k];
+        out[24 + k] = (long long)p.slot_bytes[k];
+    }
+    long long n = 80;
+    for (int kb = 0; kb < p.nb; ++kb)
+        for (int k = 0; k < p.pieces(); ++k, n += 6) {
+            if (n + 6 > cap) return -1;
+            const RenderPlan::Piece q = p.piece(kb, k);
+            const long long v[] = {q.begin, q.end, q.shard, q.chunk,
+                                   pool_plan(pi.cw, pi.ch, q.end - q.begin, pi.tri_bvh, q.chunk).chunks, p.groups_after[kb]};
+            std::memcpy(out + n, v, sizeof v);
+        }
+    return n;
 }
 
 // chunk_range (pool_order.h, TEST TOOL): (batch, chunk, first sample, end sample) of launch chunk gci

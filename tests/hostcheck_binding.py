@@ -12,7 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "hostcheck", "pt_hostcheck.cpp")
 DEPS = [SRC] + [os.path.join(ROOT, "blenderraytracer_amd", "csrc", f) for f in ("pt_core.h", "pt_path.h", "scene_pack.h",
-                                                                          "pool_order.h", "kernel_select.h", "js_math.h")]
+                                                                          "pool_order.h", "kernel_select.h", "js_math.h",
+                                                                          "pool_plan.h", "render_plan.h")]
 LIB = os.path.join(HERE, "hostcheck", "_build", "libpt_hostcheck.so")
 _lib = None
 
@@ -191,6 +192,48 @@ def pool_order(cw, ch, chunks, one_wave=True):
     n = L.ptc_pool_order(cw, ch, chunks, int(one_wave), out.ctypes.data_as(C.POINTER(C.c_uint32)), par)
     assert n == tiles * chunks
     return out, par[0], par[1], par[2]
+
+
+PLAN_IN = ("cw", "ch", "sample_begin", "sample_end", "samples", "batch_samples", "max_depth", "pool", "first", "tri_bvh",
+           "shards", "home_first", "want_segs", "want_draws", "want_preview", "err_active", "err_groups", "knobs",
+           "refuse_fused", "refuse_slots_shard")
+PLAN_DEFAULTS = dict(sample_begin=0, sample_end=0, batch_samples=0, max_depth=5, pool=1, first=0, tri_bvh=0, shards=1,
+                     home_first=1, want_segs=0, want_draws=0, want_preview=0, err_active=0, err_groups=0, knobs=7,
+                     refuse_fused=0, refuse_slots_shard=-1)
+PLAN_HEAD = ("base", "s0", "s1", "batch", "nb", "devices", "queue", "gated", "preview", "ahead", "ring", "fchunk",
+             "fdoubles", "err_chunk", "final_groups")
+DEVICE_MODES = ("one", "whole", "split")
+QUEUE_MODES = ("serial", "overlapped", "fused")
+KNOB_OVERLAP, KNOB_ITEM_CANCEL, KNOB_FUSED_BATCHES, KNOB_FUSED_PREVIEW = 1, 2, 4, 8
+_plan_out = None
+
+
+def render_plan(**kw):
+    """The plan of a render (render_plan.h plan_render) for PLAN_IN's fields by name (PLAN_DEFAULTS otherwise; knobs:
+    the KNOB_* bits, default the shipped ones).  A dict of PLAN_HEAD with devices / queue as DEVICE_MODES / QUEUE_MODES
+    strings, plus chunk_hint and slot_bytes (per shard), asks (the fit questions in order: (kind, shard, amount), kind
+    "slots" | "fused"), launches (per batch a list of (begin, end, shard, chunk, chunks)) and groups_after."""
+    L = lib()
+    L.ptc_render_plan.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.c_longlong]
+    L.ptc_render_plan.restype = C.c_longlong
+    v = dict(PLAN_DEFAULTS, **kw)
+    assert set(v) == set(PLAN_IN), sorted(set(v) ^ set(PLAN_IN))
+    global _plan_out
+    if _plan_out is None:
+        _plan_out = (C.c_longlong * (80 + 6 * 8 * 1024))()
+    out, cap = _plan_out, len(_plan_out)
+    n = L.ptc_render_plan((C.c_int * len(PLAN_IN))(*[int(v[k]) for k in PLAN_IN]), out, cap)
+    assert n >= 80, n
+    res = dict(zip(PLAN_HEAD, out[:15]))
+    res["devices"], res["queue"] = DEVICE_MODES[res["devices"]], QUEUE_MODES[res["queue"]]
+    res["chunk_hint"] = list(out[16:16 + v["shards"]])
+    res["slot_bytes"] = list(out[24:24 + v["shards"]])
+    res["asks"] = [(("slots", "fused")[out[32 + 3 * k]], out[33 + 3 * k], out[34 + 3 * k]) for k in range(min(out[15], 16))]
+    rows = [tuple(out[k:k + 6]) for k in range(80, n, 6)]
+    per = v["shards"] if res["devices"] == "split" else 1
+    res["launches"] = [[r[:5] for r in rows[k * per:(k + 1) * per]] for k in range(res["nb"])]
+    res["groups_after"] = [rows[k * per][5] for k in range(res["nb"])]
+    return res
 
 
 KNOBS = ("bvh_walk", "lean", "lds_grid", "lds_nodes", "lds_tri", "tri_lds_nodes")

@@ -1269,6 +1269,30 @@ def test_overlapped_batches_equal_serial_batches(gpu, tmp_path):
         assert np.array_equal(unfused[k], ref, equal_nan=True), k
 
 
+def test_downgraded_batches_equal_serial_batches(gpu, tmp_path):
+    """Two downgrades of the render's plan (render_plan.h) that no other test reaches, on _BATCH_SCRIPT's shapes:
+    fused buffers that do not fit (RT_FUSED_MB=0: one launch per batch, overlapped) and no overlapped batches at all
+    (RT_OVERLAP=0: batch after batch; with devices [0, 0] every batch's samples split over the two states and
+    merge_shards).  Each gives the bits of the serial batches on one device — except the [0, 0] split of every
+    batch, which adds each batch's two halves in another order (4.4e-16 from the one-device means, measured on
+    the commit before the plan was lifted out of render_impl): that one equals that commit's own output for the
+    same setting, tests/golden/split_every_batch_rtow_160x90_24spp_b5.mean_f64.gz."""
+    import gzip
+    import os
+    serial = _render_in_child(_BATCH_SCRIPT, tmp_path / "serial.npz", RT_PART_MB="1")
+    nofit = _render_in_child(_BATCH_SCRIPT, tmp_path / "nofit.npz", RT_FUSED_MB="0")
+    plain = _render_in_child(_BATCH_SCRIPT, tmp_path / "plain.npz", RT_OVERLAP="0")
+    two = "rtow.json.5.[0, 0]"
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                          "split_every_batch_rtow_160x90_24spp_b5.mean_f64.gz")
+    with gzip.open(golden) as f:
+        split = np.frombuffer(f.read(), dtype="<f8").reshape(90, 160, 3)
+    for k in serial.files:
+        ref = serial["rtow.json.5.None"] if k == two else serial[k]
+        assert np.array_equal(nofit[k], ref, equal_nan=True), k
+        assert np.array_equal(plain[k], split if k == two else ref, equal_nan=True), k
+
+
 @pytest.mark.parametrize("gamma", [2.2, 1.0, 0.45, 3.7, 0.25, 4.0, 50.0])
 def test_preview_thresholds_match_finalize(gpu, gamma):
     """preview_kernel's RGBA8 bytes (the count of gamma thresholds T_k <= tm, T_k computed with the
