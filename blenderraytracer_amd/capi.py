@@ -165,6 +165,13 @@ EXPORTS = {
     "rt_guided_filter_variance_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GuidedParams), C.c_double,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_guided_filtered_variance": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rt_hit_records": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_size_t,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "rt_shade_segments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_uint32), C.c_int32, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "rt_camera_rays": (C.c_int, [C.c_void_p, C.POINTER(Settings), C.c_int32, C.POINTER(C.c_int32), C.c_size_t,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     # include/rt_scene_json.h (host-only scene-JSON loader)
     "rt_json_scene_load": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rt_json_scene_desc": (C.POINTER(SceneDesc), [C.c_void_p]),

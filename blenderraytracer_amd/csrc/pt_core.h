@@ -1694,6 +1694,23 @@ RT_HD void set_face(Hit<R>& h, V3<R> d, V3<R> outward) {       // math.js:55-58
     h.n = h.front ? outward : outward * (R)-1;
 }
 
+// Binary32's box face where none of the reference's six compares with 1e-6 holds.  The point o + d t carries an
+// error of 2^-24 (2 |d t| + |o|) per coordinate: at a coordinate of 16 and more the spacing of binary32 alone
+// (1.9e-6 in [16, 32)) exceeds the 1e-6, a point one ulp off its face fails every compare and the reference's
+// chain ends at +z whatever face was hit (tests/test_shade.py: 258 of 800 rays that reach such boxes from far
+// away).  The point lies on the box, so the face it is nearest to is the one it is on.  Binary64 never gets here.
+template <class R>
+RT_HD V3<R> box_nearest_face(V3<R> p, const BoxRec<R>& b) {
+    R best = fabs(p.x - b.mnx), e;
+    V3<R> n = mk<R>(-1, 0, 0);
+    if ((e = fabs(p.x - b.mxx)) < best) { best = e; n = mk<R>(1, 0, 0); }
+    if ((e = fabs(p.y - b.mny)) < best) { best = e; n = mk<R>(0, -1, 0); }
+    if ((e = fabs(p.y - b.mxy)) < best) { best = e; n = mk<R>(0, 1, 0); }
+    if ((e = fabs(p.z - b.mnz)) < best) { best = e; n = mk<R>(0, 0, -1); }
+    if ((e = fabs(p.z - b.mxz)) < best) { best = e; n = mk<R>(0, 0, 1); }
+    return n;
+}
+
 // Rebuild the HitRecord of the winning primitive (point = origin + dir*t, math.js:41).  FEAT: the kinds a
 // scene without the missing features cannot hit are left out
 template <class R, int FEAT = F_ALL>
@@ -1720,7 +1737,8 @@ RT_HD Hit<R> hit_record(const SceneView<R>& sc, V3<R> o, V3<R> d, const Closest<
         else if (fabs(h.p.y - b.mny) < eps) n = mk<R>(0, -1, 0);
         else if (fabs(h.p.y - b.mxy) < eps) n = mk<R>(0, 1, 0);
         else if (fabs(h.p.z - b.mnz) < eps) n = mk<R>(0, 0, -1);
-        else n = mk<R>(0, 0, 1);
+        else if (sizeof(R) == 8 || fabs(h.p.z - b.mxz) < eps) n = mk<R>(0, 0, 1);     // binary64: the reference's rule
+        else n = box_nearest_face(h.p, b);                                            // binary32 only, see there
         set_face(h, d, n);
     } else {
         const TriRec<R> tr = sc.tris[c.idx];

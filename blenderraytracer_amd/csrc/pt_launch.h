@@ -135,6 +135,30 @@ template <class R>
 hipError_t launch_texture_values(const SceneView<R>& sc, int tex, const double* pts, size_t n, double* rgb,
                                  hipStream_t stream);
 
+// launch_closest_hits' query followed by hit_record<R, F_ALL> of the winner: rt_hit_records.  rec: n x 6 doubles
+// (point, normal; NaN on a miss), front: n bytes, mat: n ints (-1 on a miss); all device
+template <class R>
+hipError_t launch_hit_records(const SceneView<R>& sc, bool bvh, const double* rays, size_t n, double* t, int* kind,
+                              int* idx, double* rec, uint8_t* front, int* mat, hipStream_t stream);
+
+// One segment of n rays (rays n x 6 doubles, keys n x 2 words: the Rng's key and draw count; device) from throughput
+// (1, 1, 1) at `depth`: the closest hit (bvh: the general tree walk, else World order) and shade_segment<R, FEAT>
+// -> out_f (n x 12 doubles: new origin, new direction, T, L) and out_i (n x 4 ints: done, the hit's kind and index,
+// the Rng's draw count afterwards), device: rt_shade_segments.  variant: kShadeVariants' feature sets; the caller has
+// checked that the scene has nothing the variant compiled out
+constexpr int kShadeVariants = 3;          // 0 F_ALL, 1 the lean triangle-tree kernel's set, 2 the lean grid kernel's
+template <class R>
+hipError_t launch_shade_segments(const SceneView<R>& sc, bool bvh, int variant, const double* rays, const uint32_t* keys,
+                                 int depth, size_t n, double* out_f, int* out_i, hipStream_t stream);
+
+// start_sample of n (i, j, s) triples (pixels n x 3 ints, j bottom-up; device) under the image's size, AA mode and
+// seed -> out (n x 6 doubles: origin, direction) and draws (n words: the Rng's draw count), device: rt_camera_rays.
+// variant bit 0: RELOAD (the camera words read from the kernel-argument segment), bit 1: without F_CAMALL
+constexpr int kCameraVariants = 4;
+template <class R>
+hipError_t launch_camera_rays(const SceneView<R>& sc, const ImageParams& im, int variant, const int* pixels, size_t n,
+                              double* out, uint32_t* draws, hipStream_t stream);
+
 // default of rt_settings.sum_order = RT_SUM_POOL: the sample pool, unless RT_SAMPLE_POOL=0 is set in the
 // environment (A/B runs of the lane-per-pixel kernel)
 bool trace_uses_pool();

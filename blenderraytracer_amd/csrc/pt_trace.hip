@@ -1398,6 +1398,164 @@ hipError_t launch_texture_values(const SceneView<R>& sc, int tex, const double* 
 template hipError_t launch_texture_values<double>(const SceneView<double>&, int, const double*, size_t, double*, hipStream_t);
 template hipError_t launch_texture_values<float>(const SceneView<float>&, int, const double*, size_t, double*, hipStream_t);
 
+// ---- the hit record of World.hit's winner for given rays (rt_hit_records: closest_hits_kernel's query, then
+// hit_record<R, F_ALL>, the function shade_segment calls) ----
+template <class R, int ACC>
+__global__ __launch_bounds__(64) void hit_records_kernel(const SceneView<R> sc, const double* __restrict__ rays,
+                                                         const size_t n, double* __restrict__ t_out,
+                                                         int* __restrict__ kind_out, int* __restrict__ idx_out,
+                                                         double* __restrict__ rec_out, uint8_t* __restrict__ front_out,
+                                                         int* __restrict__ mat_out) {
+    BvhStack stk{nullptr, 0};
+    if constexpr (lds_form(ACC)) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
+        stk = stage_lds_wave<R, ACC>(sc, lds_dyn);
+        __syncthreads();
+    } else {
+        __shared__ int stack[RT_BVH_STACK * 64];
+        stk = BvhStack{stack + threadIdx.x, 64};
+    }
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n) return;
+    const double* q = rays + 6 * r;
+    const V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), d = mk<R>((R)q[3], (R)q[4], (R)q[5]);
+    Work w{0, 0, 0, 0, 0, 0};
+    const Closest<R> c = closest_hit_acc<R, ACC>(sc, o, d, w, stk);
+    const bool hit = c.kind != HIT_NONE;
+    t_out[r] = hit ? (double)c.t : (double)INFINITY;
+    kind_out[r] = c.kind;
+    idx_out[r] = hit ? c.idx : -1;
+    double* rec = rec_out + 6 * r;
+    if (!hit) {
+        for (int k = 0; k < 6; ++k) rec[k] = (double)NAN;
+        front_out[r] = 0;
+        mat_out[r] = -1;
+        return;
+    }
+    const Hit<R> h = hit_record<R, F_ALL>(sc, o, d, c);
+    rec[0] = (double)h.p.x; rec[1] = (double)h.p.y; rec[2] = (double)h.p.z;
+    rec[3] = (double)h.n.x; rec[4] = (double)h.n.y; rec[5] = (double)h.n.z;
+    front_out[r] = h.front ? 1 : 0;
+    mat_out[r] = h.mat;
+}
+
+// launch_closest_hits' choice of walk
+template <class R>
+hipError_t launch_hit_records(const SceneView<R>& sc, bool bvh, const double* rays, size_t n, double* t, int* kind,
+                              int* idx, double* rec, uint8_t* front, int* mat, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const KernelChoice k = choose_kernel(sc, 0, bvh, true);
+    SceneView<R> v = sc;
+    if (k.acc == ACC_BVH_TRI_LDS) v.tri_lds_nodes = k.tri_lds_nodes;
+    with_acc(k.acc, [&](auto tag) {
+        constexpr int ACC = walk_of<plain_of(decltype(tag)::value)>();
+        const size_t lb = !lds_form(ACC) ? 0 : ACC == ACC_GRID_LDS ? k.lds_bytes
+                        : WideLds{ACC == ACC_BVH_TRI_LDS ? v.tri_lds_nodes : v.num_sphere_wide,
+                                  std::min(v.stack_entries, RT_BVH_STACK)}.bytes(1);
+        hipLaunchKernelGGL((hit_records_kernel<R, ACC>), dim3((unsigned)((n + 63) / 64)), dim3(64), lb, stream,
+                           v, rays, n, t, kind, idx, rec, front, mat);
+    });
+    return hipGetLastError();
+}
+template hipError_t launch_hit_records<double>(const SceneView<double>&, bool, const double*, size_t, double*, int*, int*,
+                                               double*, uint8_t*, int*, hipStream_t);
+template hipError_t launch_hit_records<float>(const SceneView<float>&, bool, const double*, size_t, double*, int*, int*,
+                                              double*, uint8_t*, int*, hipStream_t);
+
+// ---- one segment shaded for given rays (rt_shade_segments: the closest hit, then shade_segment itself) ----
+// FEAT: F_ALL, or a lean kernel's feature set (feat_of): then shade_segment's Schlick exact path is the out-of-line
+// one where the lean triangle-tree kernel has it, and hit_record and background hold what that kernel's hold
+template <class R, int FEAT, int ACC>
+__global__ __launch_bounds__(64) void shade_segments_kernel(const SceneView<R> sc, const double* __restrict__ rays,
+                                                            const uint32_t* __restrict__ keys, const int depth0,
+                                                            const size_t n, double* __restrict__ out_f,
+                                                            int* __restrict__ out_i) {
+    __shared__ int stack[RT_BVH_STACK * 64];
+    const BvhStack stk{stack + threadIdx.x, 64};
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n) return;
+    const double* q = rays + 6 * r;
+    V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), d = mk<R>((R)q[3], (R)q[4], (R)q[5]);
+    Rng<R> g{keys[2 * r], keys[2 * r + 1]};
+    V3<R> T = mk<R>(1, 1, 1), L;
+    int depth = depth0;
+    Work w{0, 0, 0, 0, 0, 0};
+    const Closest<R> c = closest_hit_acc<R, ACC>(sc, o, d, w, stk);
+    const bool done = shade_segment<R, FEAT, ACC>(sc, c, o, d, T, depth, g, L);
+    double* f = out_f + 12 * r;
+    f[0] = (double)o.x; f[1] = (double)o.y; f[2] = (double)o.z;
+    f[3] = (double)d.x; f[4] = (double)d.y; f[5] = (double)d.z;
+    f[6] = (double)T.x; f[7] = (double)T.y; f[8] = (double)T.z;
+    f[9] = (double)L.x; f[10] = (double)L.y; f[11] = (double)L.z;
+    int* k = out_i + 4 * r;
+    k[0] = done ? 1 : 0;
+    k[1] = c.kind;
+    k[2] = c.kind == HIT_NONE ? -1 : c.idx;
+    k[3] = (int)g.k;
+}
+
+template <class R>
+hipError_t launch_shade_segments(const SceneView<R>& sc, bool bvh, int variant, const double* rays, const uint32_t* keys,
+                                 int depth, size_t n, double* out_f, int* out_i, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (variant < 0 || variant >= kShadeVariants) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + 63) / 64));
+    auto go = [&](auto feat) {
+        constexpr int FEAT = decltype(feat)::value;
+        if (bvh) hipLaunchKernelGGL((shade_segments_kernel<R, FEAT, ACC_BVH_STACK>), grid, dim3(64), 0, stream, sc, rays, keys, depth, n, out_f, out_i);
+        else hipLaunchKernelGGL((shade_segments_kernel<R, FEAT, ACC_BRUTE>), grid, dim3(64), 0, stream, sc, rays, keys, depth, n, out_f, out_i);
+    };
+    if (variant == 0) go(std::integral_constant<int, F_ALL>{});
+    else if (variant == 1) go(std::integral_constant<int, feat_of<ACC_BVH_STACK_LEAN>()>{});
+    else go(std::integral_constant<int, feat_of<ACC_GRID_LDS_LEAN>()>{});
+    return hipGetLastError();
+}
+template hipError_t launch_shade_segments<double>(const SceneView<double>&, bool, int, const double*, const uint32_t*, int,
+                                                  size_t, double*, int*, hipStream_t);
+template hipError_t launch_shade_segments<float>(const SceneView<float>&, bool, int, const double*, const uint32_t*, int,
+                                                 size_t, double*, int*, hipStream_t);
+
+// ---- the camera ray of given (pixel, sample)s (rt_camera_rays: start_sample) ----
+// SceneView is the kernel's first argument: RELOAD reads the camera words at offsetof(SceneView, cam_o) of the
+// kernel-argument segment, as in the trace kernels (TraceArgs)
+template <class R, bool RELOAD, int FEAT>
+__global__ __launch_bounds__(64) void camera_rays_kernel(const SceneView<R> sc, const ImageParams im,
+                                                         const int* __restrict__ pixels, const size_t n,
+                                                         double* __restrict__ out, uint32_t* __restrict__ draws) {
+    const size_t r = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (r >= n) return;
+    const int i = pixels[3 * r], j = pixels[3 * r + 1], s = pixels[3 * r + 2];
+    const int row = im.height - 1 - j;
+    const uint32_t pkey = pixel_key(im.seedm, (uint32_t)row * (uint32_t)im.width + (uint32_t)i);
+    Rng<R> g;
+    V3<R> o, d;
+    start_sample<R, RELOAD, FEAT>(sc, im, i, j, pkey, s, g, o, d);
+    double* f = out + 6 * r;
+    f[0] = (double)o.x; f[1] = (double)o.y; f[2] = (double)o.z;
+    f[3] = (double)d.x; f[4] = (double)d.y; f[5] = (double)d.z;
+    draws[r] = g.k;
+}
+
+template <class R>
+hipError_t launch_camera_rays(const SceneView<R>& sc, const ImageParams& im, int variant, const int* pixels, size_t n,
+                              double* out, uint32_t* draws, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (variant < 0 || variant >= kCameraVariants) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((n + 63) / 64));
+    constexpr int LEAN = F_ALL & ~F_CAMALL;
+    switch (variant) {
+    case 0: hipLaunchKernelGGL((camera_rays_kernel<R, false, F_ALL>), grid, dim3(64), 0, stream, sc, im, pixels, n, out, draws); break;
+    case 1: hipLaunchKernelGGL((camera_rays_kernel<R, true, F_ALL>), grid, dim3(64), 0, stream, sc, im, pixels, n, out, draws); break;
+    case 2: hipLaunchKernelGGL((camera_rays_kernel<R, false, LEAN>), grid, dim3(64), 0, stream, sc, im, pixels, n, out, draws); break;
+    default: hipLaunchKernelGGL((camera_rays_kernel<R, true, LEAN>), grid, dim3(64), 0, stream, sc, im, pixels, n, out, draws); break;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_camera_rays<double>(const SceneView<double>&, const ImageParams&, int, const int*, size_t, double*,
+                                               uint32_t*, hipStream_t);
+template hipError_t launch_camera_rays<float>(const SceneView<float>&, const ImageParams&, int, const int*, size_t, double*,
+                                              uint32_t*, hipStream_t);
+
 // ---- multi-device sample split: dst += src elementwise (the shards' sums / counters, in shard order) ----
 template <class T>
 __global__ __launch_bounds__(256) void add_kernel(T* __restrict__ dst, const T* __restrict__ src, const size_t n) {

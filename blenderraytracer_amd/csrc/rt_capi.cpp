@@ -2071,6 +2071,139 @@ int rt_closest_hits(rt_scene* sc, int32_t precision, int32_t accel, const double
     return RT_OK;
 }
 
+int rt_hit_records(rt_scene* sc, int32_t precision, int32_t accel, const double* rays, size_t n, double* t, int32_t* kind,
+                   int32_t* index, double* point, double* normal, uint8_t* front, int32_t* mat) {
+    if (!sc || (n > 0 && !rays)) return fail(RT_ERR_INVALID, "NULL argument");
+    if (precision != RT_PREC_F64 && precision != RT_PREC_F32) return fail(RT_ERR_INVALID, "precision %d", precision);
+    rt_settings s{};
+    s.accel = accel;
+    if (s.accel < RT_ACCEL_AUTO || s.accel > RT_ACCEL_BVH) return fail(RT_ERR_INVALID, "accel %d", accel);
+    int rc = check_accel(sc, &s);
+    if (rc) return rc;
+    if (n == 0) return RT_OK;
+    DeviceState& ds = sc->home;
+    HIP_TRY(hipSetDevice(ds.device));
+    DevBuf<double> d_rays, d_t, d_rec;
+    DevBuf<int> d_kind, d_idx, d_mat;
+    DevBuf<uint8_t> d_front;
+    hipError_t e = d_rays.ensure(6 * n);
+    if (e == hipSuccess) e = d_t.ensure(n);
+    if (e == hipSuccess) e = d_rec.ensure(6 * n);
+    if (e == hipSuccess) e = d_kind.ensure(n);
+    if (e == hipSuccess) e = d_idx.ensure(n);
+    if (e == hipSuccess) e = d_mat.ensure(n);
+    if (e == hipSuccess) e = d_front.ensure(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays.p, rays, 6 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
+    const bool bvh = use_bvh(sc, &s);
+    if (e == hipSuccess)
+        e = with_view(ds, precision, [&](const auto& v) {
+            return launch_hit_records(v, bvh, d_rays.p, n, d_t.p, d_kind.p, d_idx.p, d_rec.p, d_front.p, d_mat.p, ds.stream);
+        });
+    // the device rows are point then normal; the host gets them as two n x 3 arrays
+    std::vector<double> rec(point || normal ? 6 * n : 0);
+    if (e == hipSuccess && t) e = hipMemcpyAsync(t, d_t.p, n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && kind) e = hipMemcpyAsync(kind, d_kind.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && index) e = hipMemcpyAsync(index, d_idx.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && mat) e = hipMemcpyAsync(mat, d_mat.p, n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && front) e = hipMemcpyAsync(front, d_front.p, n, hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && !rec.empty())
+        e = hipMemcpyAsync(rec.data(), d_rec.p, 6 * n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_rays.release(); d_t.release(); d_rec.release(); d_kind.release(); d_idx.release(); d_mat.release(); d_front.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_hit_records: %s", hipGetErrorString(e));
+    for (size_t r = 0; r < n && !rec.empty(); ++r)
+        for (int k = 0; k < 3; ++k) {
+            if (point) point[3 * r + k] = rec[6 * r + k];
+            if (normal) normal[3 * r + k] = rec[6 * r + 3 + k];
+        }
+    return RT_OK;
+}
+
+int rt_shade_segments(rt_scene* sc, int32_t precision, int32_t accel, int32_t variant, const double* rays,
+                      const uint32_t* keys, int32_t depth, size_t n, double* out_f, int32_t* out_i) {
+    if (!sc || (n > 0 && (!rays || !keys))) return fail(RT_ERR_INVALID, "NULL argument");
+    if (precision != RT_PREC_F64 && precision != RT_PREC_F32) return fail(RT_ERR_INVALID, "precision %d", precision);
+    if (variant < 0 || variant >= kShadeVariants) return fail(RT_ERR_INVALID, "variant %d", variant);
+    rt_settings s{};
+    s.accel = accel;
+    if (s.accel < RT_ACCEL_AUTO || s.accel > RT_ACCEL_BVH) return fail(RT_ERR_INVALID, "accel %d", accel);
+    int rc = check_accel(sc, &s);
+    if (rc) return rc;
+    DeviceState& ds = sc->home;
+    // what the variant's feature set compiled out (the lean kernels' conditions, kernel_select.h) must not be there
+    const char* missing = with_view(ds, precision, [&](const auto& v) -> const char* {
+        if (v.num_tex > 0) return "procedural textures";
+        if (variant == 0) return nullptr;
+        if (v.background != RT_BG_GRADIENT) return "a background other than the gradient";
+        if (v.num_boxes > 0) return "boxes";
+        if (variant == 2 && (v.num_planes > 0 || sc->desc.d.num_triangles > 0)) return "planes or triangles";
+        return nullptr;
+    });
+    if (missing) return fail(RT_ERR_INVALID, "rt_shade_segments: the scene has %s, which variant %d leaves out", missing, variant);
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(ds.device));
+    DevBuf<double> d_rays, d_f;
+    DevBuf<uint32_t> d_keys;
+    DevBuf<int> d_i;
+    hipError_t e = d_rays.ensure(6 * n);
+    if (e == hipSuccess) e = d_keys.ensure(2 * n);
+    if (e == hipSuccess) e = d_f.ensure(12 * n);
+    if (e == hipSuccess) e = d_i.ensure(4 * n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rays.p, rays, 6 * n * sizeof(double), hipMemcpyHostToDevice, ds.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_keys.p, keys, 2 * n * sizeof(uint32_t), hipMemcpyHostToDevice, ds.stream);
+    const bool bvh = use_bvh(sc, &s);
+    if (e == hipSuccess)
+        e = with_view(ds, precision, [&](const auto& v) {
+            return launch_shade_segments(v, bvh, variant, d_rays.p, d_keys.p, depth, n, d_f.p, d_i.p, ds.stream);
+        });
+    if (e == hipSuccess && out_f) e = hipMemcpyAsync(out_f, d_f.p, 12 * n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && out_i) e = hipMemcpyAsync(out_i, d_i.p, 4 * n * sizeof(int), hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_rays.release(); d_keys.release(); d_f.release(); d_i.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_shade_segments: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_camera_rays(rt_scene* sc, const rt_settings* s, int32_t variant, const int32_t* pixels, size_t n, double* out,
+                   uint32_t* draws) {
+    if (!sc || (n > 0 && !pixels)) return fail(RT_ERR_INVALID, "NULL argument");
+    int cw, ch;
+    const int rc = check_settings(s, &cw, &ch);
+    if (rc) return rc;
+    if (variant < 0 || variant >= kCameraVariants) return fail(RT_ERR_INVALID, "variant %d", variant);
+    if ((variant & 2) && (sc->desc.d.camera.type != RT_CAM_PERSPECTIVE || s->aa_mode != RT_AA_SUPERSAMPLING))
+        return fail(RT_ERR_INVALID, "rt_camera_rays: variant %d is the lean kernels' (perspective camera, supersampling)", variant);
+    for (size_t r = 0; r < n; ++r)
+        if (pixels[3 * r] < 0 || pixels[3 * r] >= s->width || pixels[3 * r + 1] < 0 || pixels[3 * r + 1] >= s->height ||
+            pixels[3 * r + 2] < 0)
+            return fail(RT_ERR_INVALID, "pixels[%zu] = (%d, %d, %d) outside %dx%d", r, pixels[3 * r], pixels[3 * r + 1],
+                        pixels[3 * r + 2], s->width, s->height);
+    if (n == 0) return RT_OK;
+    DeviceState& ds = sc->home;
+    HIP_TRY(hipSetDevice(ds.device));
+    const ImageParams im = image_params(s, cw, ch);
+    DevBuf<int> d_pix;
+    DevBuf<double> d_out;
+    DevBuf<uint32_t> d_draws;
+    hipError_t e = d_pix.ensure(3 * n);
+    if (e == hipSuccess) e = d_out.ensure(6 * n);
+    if (e == hipSuccess) e = d_draws.ensure(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pix.p, pixels, 3 * n * sizeof(int), hipMemcpyHostToDevice, ds.stream);
+    if (e == hipSuccess)
+        e = with_view(ds, s->precision, [&](const auto& v) {
+            return launch_camera_rays(v, im, variant, d_pix.p, n, d_out.p, d_draws.p, ds.stream);
+        });
+    if (e == hipSuccess && out) e = hipMemcpyAsync(out, d_out.p, 6 * n * sizeof(double), hipMemcpyDeviceToHost, ds.stream);
+    if (e == hipSuccess && draws) e = hipMemcpyAsync(draws, d_draws.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ds.stream);
+    const hipError_t es = hipStreamSynchronize(ds.stream);
+    if (e == hipSuccess) e = es;
+    d_pix.release(); d_out.release(); d_draws.release();
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_camera_rays: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
 int rt_occluded(rt_scene* sc, int32_t precision, int32_t accel, const double* rays, const double* tmax, size_t n,
                 uint8_t* out) {
     if (!sc || (n > 0 && (!rays || !tmax || !out))) return fail(RT_ERR_INVALID, "NULL argument");

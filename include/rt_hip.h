@@ -558,6 +558,40 @@ int rt_guided_filtered_variance(rt_scene* scene, double* var);
  * see rt_render). */
 int rt_cancel(rt_scene* scene);
 
+/* Diagnostic (tests): the hit record the trace kernels rebuild at World.hit's winner, for `n` rays on the scene's
+ * device: rt_closest_hits' query (same rays layout, precision rounding and accel) followed by the function the
+ * shading stage calls on its result.  Outputs (host, any may be NULL): t, kind and index as rt_closest_hits
+ * reports them; point and normal (n x 3 doubles each: origin + direction * t and the normal turned against the
+ * ray), front (n bytes, 1: the ray met the outward side) and mat (n: the material's index in the scene).  A row
+ * without a hit gets NaN in point and normal, front 0 and mat -1. */
+int rt_hit_records(rt_scene* scene, int32_t precision, int32_t accel, const double* rays, size_t n, double* t,
+                   int32_t* kind, int32_t* index, double* point, double* normal, uint8_t* front, int32_t* mat);
+
+/* Diagnostic (tests): one path segment of the trace kernels for `n` rays on the scene's device.  Ray r starts with
+ * the random stream {key = keys[2 r], draws so far = keys[2 r + 1]}, throughput (1, 1, 1) and `depth` bounces left;
+ * its closest hit is found as the trace kernels find it (rays, precision and accel as rt_closest_hits; RT_ACCEL_BVH
+ * is the general tree walk) and handed to the kernels' own shading function: emission, scatter or background.
+ * out_f (host, n x 12 doubles, may be NULL): the next ray's origin and direction, the throughput T and the radiance
+ * L the segment ends the path with; out_i (host, n x 4, may be NULL): done (1: the path ended; origin, direction and
+ * T are then whatever the function left), the hit's kind and index as rt_closest_hits reports them, and the stream's
+ * draw count afterwards.  Any scene without procedural textures, an empty one included (every ray then gets the
+ * background); scene lights and emitter sampling are not evaluated.  variant: 0 the general feature set; 1 the lean
+ * triangle-tree kernel's (spheres, planes, triangles; the sky gradient) with its out-of-line exact Schlick path;
+ * 2 the lean grid kernel's (spheres alone; the sky gradient).  RT_ERR_INVALID when the scene has what the variant
+ * leaves out. */
+int rt_shade_segments(rt_scene* scene, int32_t precision, int32_t accel, int32_t variant, const double* rays,
+                      const uint32_t* keys, int32_t depth, size_t n, double* out_f, int32_t* out_i);
+
+/* Diagnostic (tests): the camera ray the trace kernels start sample s of pixel (i, j) with (j counted from the
+ * bottom row, as getRay's t), for `n` triples pixels[3 r ..] = (i, j, s) on the scene's device.  Of the settings
+ * width, height, aa_mode, seed and precision are read (the pixel's key is the render's).  out (host, n x 6 doubles,
+ * may be NULL): origin and direction; draws (host, n, may be NULL): random numbers the sample start consumed.
+ * variant bit 0: the camera is read from the kernel-argument segment at every sample start, as the binary32 and the
+ * lean grid kernels read it; bit 1: the lean kernels' form without orthographic cameras and without the stochastic
+ * and centre AA modes (RT_ERR_INVALID for a scene or settings that need them).  All four give the same bits. */
+int rt_camera_rays(rt_scene* scene, const rt_settings* settings, int32_t variant, const int32_t* pixels, size_t n,
+                   double* out, uint32_t* draws);
+
 #ifdef __cplusplus
 }
 #endif

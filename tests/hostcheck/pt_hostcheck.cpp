@@ -342,6 +342,122 @@ extern "C" int ptc_walk_hits_kind(const rt_scene_desc* d, int walk, const double
     return walk_hits(d, walk, rays, n, t, kind, idx);
 }
 
+// rt_hit_records on the CPU (the same contract: tests/test_shade.py compares it with tests/shade_ref.py):
+// closest_hit_acc (accel RT_ACCEL_BVH: the general ordered walk, else World order), then hit_record<R, F_ALL>
+template <class R>
+static int hit_records(const rt_scene_desc* d, int accel, const double* rays, long long n, double* t, int* kind, int* idx,
+                       double* point, double* normal, unsigned char* front, int* mat) {
+    HostView<R> hv;
+    if (!hv.init(d)) return -1;
+    int stack[64];
+    const BvhStack stk{stack, 1};
+    for (long long r = 0; r < n; ++r) {
+        const double* q = rays + 6 * r;
+        const V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), dir = mk<R>((R)q[3], (R)q[4], (R)q[5]);
+        Work w{};
+        const Closest<R> c = accel == RT_ACCEL_BVH ? closest_hit_acc<R, ACC_BVH_STACK>(hv.v, o, dir, w, stk)
+                                                   : closest_hit_acc<R, ACC_BRUTE>(hv.v, o, dir, w, stk);
+        const bool hit = c.kind != HIT_NONE;
+        if (t) t[r] = hit ? (double)c.t : (double)INFINITY;
+        if (kind) kind[r] = c.kind;
+        if (idx) idx[r] = hit ? c.idx : -1;
+        Hit<R> h{};
+        if (hit) h = hit_record<R, F_ALL>(hv.v, o, dir, c);
+        const double p3[3] = {(double)h.p.x, (double)h.p.y, (double)h.p.z}, n3[3] = {(double)h.n.x, (double)h.n.y, (double)h.n.z};
+        for (int k = 0; k < 3; ++k) {
+            if (point) point[3 * r + k] = hit ? p3[k] : (double)NAN;
+            if (normal) normal[3 * r + k] = hit ? n3[k] : (double)NAN;
+        }
+        if (front) front[r] = hit && h.front ? 1 : 0;
+        if (mat) mat[r] = hit ? h.mat : -1;
+    }
+    return 0;
+}
+extern "C" int ptc_hit_records(const rt_scene_desc* d, int precision, int accel, const double* rays, long long n, double* t,
+                               int* kind, int* idx, double* point, double* normal, unsigned char* front, int* mat) {
+    return precision == RT_PREC_F32 ? hit_records<float>(d, accel, rays, n, t, kind, idx, point, normal, front, mat)
+                                    : hit_records<double>(d, accel, rays, n, t, kind, idx, point, normal, front, mat);
+}
+
+// rt_shade_segments on the CPU (the same contract and variants; -2: the scene has what the variant leaves out)
+template <class R, int FEAT>
+static void shade_segments(const SceneView<R>& v, bool bvh, const double* rays, const unsigned* keys, int depth0, long long n,
+                           double* out_f, int* out_i) {
+    int stack[64];
+    const BvhStack stk{stack, 1};
+    for (long long r = 0; r < n; ++r) {
+        const double* q = rays + 6 * r;
+        V3<R> o = mk<R>((R)q[0], (R)q[1], (R)q[2]), dir = mk<R>((R)q[3], (R)q[4], (R)q[5]);
+        Rng<R> g{keys[2 * r], keys[2 * r + 1]};
+        V3<R> T = mk<R>(1, 1, 1), L;
+        int depth = depth0;
+        Work w{};
+        const Closest<R> c = bvh ? closest_hit_acc<R, ACC_BVH_STACK>(v, o, dir, w, stk) : closest_hit_acc<R, ACC_BRUTE>(v, o, dir, w, stk);
+        const bool done = bvh ? shade_segment<R, FEAT, ACC_BVH_STACK>(v, c, o, dir, T, depth, g, L)
+                              : shade_segment<R, FEAT, ACC_BRUTE>(v, c, o, dir, T, depth, g, L);
+        const double f[12] = {(double)o.x, (double)o.y, (double)o.z, (double)dir.x, (double)dir.y, (double)dir.z,
+                              (double)T.x, (double)T.y, (double)T.z, (double)L.x, (double)L.y, (double)L.z};
+        if (out_f) std::memcpy(out_f + 12 * r, f, sizeof f);
+        if (out_i) {
+            out_i[4 * r] = done ? 1 : 0;
+            out_i[4 * r + 1] = c.kind;
+            out_i[4 * r + 2] = c.kind == HIT_NONE ? -1 : c.idx;
+            out_i[4 * r + 3] = (int)g.k;
+        }
+    }
+}
+template <class R>
+static int shade_segments_of(const rt_scene_desc* d, int accel, int variant, const double* rays, const unsigned* keys, int depth,
+                             long long n, double* out_f, int* out_i) {
+    HostView<R> hv;
+    if (!hv.init(d) || variant < 0 || variant > 2) return -1;
+    const SceneView<R>& v = hv.v;
+    if (variant > 0 && (v.background != RT_BG_GRADIENT || v.num_boxes > 0)) return -2;
+    if (variant == 2 && (v.num_planes > 0 || d->num_triangles > 0)) return -2;
+    const bool bvh = accel == RT_ACCEL_BVH;
+    if (variant == 0) shade_segments<R, F_ALL>(v, bvh, rays, keys, depth, n, out_f, out_i);
+    else if (variant == 1) shade_segments<R, feat_of<ACC_BVH_STACK_LEAN>()>(v, bvh, rays, keys, depth, n, out_f, out_i);
+    else shade_segments<R, feat_of<ACC_GRID_LDS_LEAN>()>(v, bvh, rays, keys, depth, n, out_f, out_i);
+    return 0;
+}
+extern "C" int ptc_shade_segments(const rt_scene_desc* d, int precision, int accel, int variant, const double* rays,
+                                  const unsigned* keys, int depth, long long n, double* out_f, int* out_i) {
+    return precision == RT_PREC_F32 ? shade_segments_of<float>(d, accel, variant, rays, keys, depth, n, out_f, out_i)
+                                    : shade_segments_of<double>(d, accel, variant, rays, keys, depth, n, out_f, out_i);
+}
+
+// rt_camera_rays on the CPU (variant bit 0, the kernel-argument reload, is the device's alone: the same function
+// here; bit 1: without F_CAMALL, -2 for an orthographic camera or another AA mode)
+template <class R>
+static int camera_rays(const rt_scene_desc* d, const rt_settings* s, int variant, const int* pixels, long long n, double* out,
+                       unsigned* draws) {
+    HostView<R> hv;
+    if (!hv.init(d) || variant < 0 || variant > 3) return -1;
+    if ((variant & 2) && (d->camera.type != RT_CAM_PERSPECTIVE || s->aa_mode != RT_AA_SUPERSAMPLING)) return -2;
+    ImageParams im{};
+    im.width = s->width; im.height = s->height;
+    im.aa_mode = s->aa_mode;
+    im.seedm = host_seed_mix(s->seed);
+    for (long long r = 0; r < n; ++r) {
+        const int i = pixels[3 * r], j = pixels[3 * r + 1], smp = pixels[3 * r + 2];
+        const int row = im.height - 1 - j;
+        const uint32_t pkey = pixel_key(im.seedm, (uint32_t)row * (uint32_t)im.width + (uint32_t)i);
+        Rng<R> g;
+        V3<R> o, dir;
+        if (variant & 2) start_sample<R, false, F_ALL & ~F_CAMALL>(hv.v, im, i, j, pkey, smp, g, o, dir);
+        else start_sample<R, false, F_ALL>(hv.v, im, i, j, pkey, smp, g, o, dir);
+        const double f[6] = {(double)o.x, (double)o.y, (double)o.z, (double)dir.x, (double)dir.y, (double)dir.z};
+        if (out) std::memcpy(out + 6 * r, f, sizeof f);
+        if (draws) draws[r] = g.k;
+    }
+    return 0;
+}
+extern "C" int ptc_camera_rays(const rt_scene_desc* d, const rt_settings* s, int variant, const int* pixels, long long n,
+                               double* out, unsigned* draws) {
+    return s->precision == RT_PREC_F32 ? camera_rays<float>(d, s, variant, pixels, n, out, draws)
+                                       : camera_rays<double>(d, s, variant, pixels, n, out, draws);
+}
+
 // The grid's binary32 geometry as the walk reads it (build_grid): out = {lo xyz, cell size xyz, grid_far};
 // n3 = cells per axis (0 0 0: no grid); *largest = the most records registered in one cell
 extern "C" int ptc_grid_geometry(const rt_scene_desc* d, double* out, int* n3, int* largest) {

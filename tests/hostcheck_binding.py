@@ -129,6 +129,60 @@ def walk_hits_kind(packed, walk, rays, L=None):
     return t, kind, idx
 
 
+def hit_records(packed, precision, accel, rays, L=None):
+    """rt_hit_records on the CPU: dict(t, kind, idx, point, normal, front, mat) of n x 6 rays."""
+    L = L or lib()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    L.ptc_hit_records.argtypes = [C.POINTER(capi.SceneDesc), C.c_int, C.c_int, dp, C.c_longlong, dp, ip, ip, dp, dp,
+                                  C.POINTER(C.c_uint8), ip]
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    n = len(rays)
+    out = {"t": np.zeros(n), "kind": np.full(n, -2, dtype=np.int32), "idx": np.full(n, -2, dtype=np.int32),
+           "point": np.zeros((n, 3)), "normal": np.zeros((n, 3)), "front": np.full(n, 2, dtype=np.uint8),
+           "mat": np.full(n, -2, dtype=np.int32)}
+    assert L.ptc_hit_records(C.byref(packed.desc), precision, accel, rays.ctypes.data_as(dp), n, out["t"].ctypes.data_as(dp),
+                             out["kind"].ctypes.data_as(ip), out["idx"].ctypes.data_as(ip), out["point"].ctypes.data_as(dp),
+                             out["normal"].ctypes.data_as(dp), out["front"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                             out["mat"].ctypes.data_as(ip)) == 0
+    return out
+
+
+def shade_segments(packed, precision, accel, rays, keys, depth, variant=0, L=None):
+    """rt_shade_segments on the CPU: (out_f n x 12: origin, direction, T, L; out_i n x 4: done, kind, index, draws),
+    or None when the scene has what the variant leaves out."""
+    L = L or lib()
+    dp, ip, up = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+    L.ptc_shade_segments.argtypes = [C.POINTER(capi.SceneDesc), C.c_int, C.c_int, C.c_int, dp, up, C.c_int, C.c_longlong, dp, ip]
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1, 2)
+    assert len(keys) == len(rays)
+    out_f = np.zeros((len(rays), 12))
+    out_i = np.full((len(rays), 4), -2, dtype=np.int32)
+    rc = L.ptc_shade_segments(C.byref(packed.desc), precision, accel, variant, rays.ctypes.data_as(dp), keys.ctypes.data_as(up),
+                              depth, len(rays), out_f.ctypes.data_as(dp), out_i.ctypes.data_as(ip))
+    if rc == -2:
+        return None
+    assert rc == 0
+    return out_f, out_i
+
+
+def camera_rays(packed, settings, pixels, variant=0, L=None):
+    """rt_camera_rays on the CPU: (out n x 6: origin, direction; draws n), or None when the variant refuses the camera
+    or the AA mode."""
+    L = L or lib()
+    dp, ip, up = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+    L.ptc_camera_rays.argtypes = [C.POINTER(capi.SceneDesc), C.POINTER(capi.Settings), C.c_int, ip, C.c_longlong, dp, up]
+    pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 3)
+    out = np.zeros((len(pixels), 6))
+    draws = np.zeros(len(pixels), dtype=np.uint32)
+    rc = L.ptc_camera_rays(C.byref(packed.desc), C.byref(settings), variant, pixels.ctypes.data_as(ip), len(pixels),
+                           out.ctypes.data_as(dp), draws.ctypes.data_as(up))
+    if rc == -2:
+        return None
+    assert rc == 0
+    return out, draws
+
+
 def grid_geometry(packed):
     """build_grid's result as the walk reads it: dict(lo, cs (binary32 values), n (cells per axis; zeros: no
     grid), far (grid_far), largest (most records in one cell))."""
