@@ -107,6 +107,22 @@ def build_lib(force=False):
     return target
 
 
+def build_variant(name, defines, force=False):
+    """lib/librt_hip_<name>.so: the library with the trace kernels' translation unit (pt_trace.hip) compiled with
+    `defines` and the default build's other objects — the twin a GPU test or an A/B run loads through RT_HIP_LIB
+    (coop0: RT_COOP_SPHERE=0, every lane's own unit-sphere loop; tests/test_coop_sphere_gpu.py)."""
+    base = build_lib(force=False)
+    target = os.path.join(LIBDIR, f"librt_hip_{name}.so")
+    if not force and not _stale(target, [base]):
+        return target
+    obj = os.path.join(LIBDIR, f"pt_trace_{name}.o")
+    _run([HIPCC, *HIP_FLAGS, *SOURCE_FLAGS.get("pt_trace.hip", []), *[f"-D{d}" for d in defines], "-c",
+          os.path.join(CSRC, "pt_trace.hip"), "-o", obj])
+    objs = [obj if src == "pt_trace.hip" else os.path.join(LIBDIR, os.path.splitext(src)[0] + ".o") for src in SOURCES]
+    _run([HIPCC, "-shared", f"--offload-arch={ARCH}", "-o", target, *objs])
+    return target
+
+
 def build_napi(force=False):
     """Node N-API addon: plain g++ against node_api.h, links librt_hip.so by rpath."""
     node_inc = os.environ.get("NODE_INCLUDE", "/usr/include/node")

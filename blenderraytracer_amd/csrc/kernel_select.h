@@ -106,8 +106,14 @@ template <class R, int ACC>
 constexpr long long lds_budget(int fewer_workgroups = 0) {
     return 160 * 1024 / (4 * waves_per_simd<R, ACC>() / lds_waves<R, ACC>() - fewer_workgroups);
 }
+// RT_COOP_SPHERE: the binary64 lean grid kernel's waves also hold unit_sphere_point's hand-off slots (pt_path.h:
+// 64 slots of 16 B per wave)
 template <class R, int ACC>
-constexpr long long lds_fixed_bytes() { return (long long)lds_waves<R, ACC>() * 3 * 64 * 8 + 256; }
+constexpr long long coop_lds_bytes() {
+    return RT_COOP_SPHERE && sizeof(R) == 8 && ACC == ACC_GRID_LDS_LEAN ? (long long)lds_waves<R, ACC>() * 64 * 16 : 0;
+}
+template <class R, int ACC>
+constexpr long long lds_fixed_bytes() { return (long long)lds_waves<R, ACC>() * 3 * 64 * 8 + 256 + coop_lds_bytes<R, ACC>(); }
 
 // ---- the knobs (A/B runs): compile-time defaults, overridden from the environment once per process ----
 // Which sphere-only launches read the nodes from LDS: binary32 (RTOW 256 spp, 6 waves/SIMD: 9752 vs
@@ -254,8 +260,12 @@ KernelChoice select_kernel(const SceneFacts& s, int aa_mode, bool bvh, bool pool
         // the grid's cell offsets and records in LDS whenever the copy fits (RT_MAT_LDS: with the material
         // records, one workgroup per CU fewer)
         const size_t b = ((s.grid_lds_bytes + 15) & ~(size_t)15) + (RT_MAT_LDS ? sizeof(MatRec<R>) * (size_t)s.num_mats : 0);
-        if ((long long)b + lds_fixed_bytes<R, ACC_GRID_LDS>() <= lds_budget<R, ACC_GRID_LDS>(RT_MAT_LDS ? 1 : 0))
-            return KernelChoice{lean(feat_of<ACC_GRID_LDS_LEAN>()) ? ACC_GRID_LDS_LEAN : ACC_GRID_LDS, true, b, 0};
+        // (the lean form's fixed part is the larger in binary64, coop_lds_bytes: a copy that fits only without it
+        // takes the general form)
+        const long long budget = lds_budget<R, ACC_GRID_LDS>(RT_MAT_LDS ? 1 : 0);
+        if (lean(feat_of<ACC_GRID_LDS_LEAN>()) && (long long)b + lds_fixed_bytes<R, ACC_GRID_LDS_LEAN>() <= budget)
+            return KernelChoice{ACC_GRID_LDS_LEAN, true, b, 0};
+        if ((long long)b + lds_fixed_bytes<R, ACC_GRID_LDS>() <= budget) return KernelChoice{ACC_GRID_LDS, true, b, 0};
     }
     // the sphere tree's nodes in LDS: binary32, binary64 only with RT_LDS_NODES=2, when the tree fits
     if (walk == ACC_BVH_SPHERES && k.lds_nodes >= (sizeof(R) == 8 ? 2 : 1) && s.num_sphere_wide > 0) {

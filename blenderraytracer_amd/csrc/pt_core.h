@@ -1763,6 +1763,67 @@ RT_HD V3<R> random_in_unit_sphere(Rng<R>& g) {                  // math.js:22-26
     return mk((R)x * (R)0x1p-23, (R)y * (R)0x1p-23, (R)z * (R)0x1p-23);
 }
 
+// ---- RT_COOP_SPHERE: random_in_unit_sphere's rejection rounds shared across the wave --------------------
+// (pt_path.h unit_sphere_point; the binary64 lean grid kernel and rt_shade_segments' variant 2; 0: every
+// lane runs its own loop, A/B.)  Draw number k is a pure function of (key, k), so any lane can evaluate any
+// round of any other lane.  In one trip the H active lanes (ranks h = 0 .. H-1, compacted) serve the n lanes
+// that still need a point (ranks 0 .. n-1): helper h evaluates, for requester q = h mod n, the round at
+// offset j = h div n from the requester's k.  Requester rho so gets the c = H div n + (rho < H mod n)
+// consecutive rounds 0 .. c-1 and takes the lowest accepted one: the sequential loop's decisions, draw for
+// draw (tests/test_coop_sphere.py emulates a wave over these functions).
+#ifndef RT_COOP_SPHERE
+#define RT_COOP_SPHERE 1
+#endif
+// the round that draws k, k+1, k+2 of stream `key`: the raw 24-bit draws, and whether the point is accepted
+// (random_in_unit_sphere's exact integer test)
+RT_HD bool sphere_round(uint32_t key, uint32_t k, uint32_t& ux, uint32_t& uy, uint32_t& uz) {
+    Rng<double> g{key, k};
+    ux = g.next_u24(); uy = g.next_u24(); uz = g.next_u24();
+    const int64_t x = (int64_t)ux - (1 << 23), y = (int64_t)uy - (1 << 23), z = (int64_t)uz - (1 << 23);
+    return x * x + y * y + z * z < ((int64_t)1 << 46);
+}
+// 1 / n for coop_assign (n in [1, 64]); the device's v_rcp_f32 is within an ulp, which coop_assign absorbs
+RT_HD float coop_rcp(uint32_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_rcpf((float)(int)(n & 0x7Fu));
+#else
+    return 1.0f / (float)(int)(n & 0x7Fu);
+#endif
+}
+// helper rank h -> (requester rank q = h mod n, round offset j = h div n), h <= 64, rn = coop_rcp(n):
+// (h + 1/2) / n lies at least 1 / (2 n) >= 2^-7 from an integer and below 65, so the binary32 product
+// (error < 2^-16) truncates to h div n.  (The conversions are the signed ones and h, n and j are masked to their
+// seven bits: the device then converts in one instruction and multiplies with its full-rate 24-bit forms.)
+struct CoopShare { uint32_t q, j; };
+RT_HD CoopShare coop_assign(uint32_t h, uint32_t n, float rn) {
+    const uint32_t j = (uint32_t)(int)(((float)(int)(h & 0x7Fu) + 0.5f) * rn) & 0x7Fu;
+    return CoopShare{h - j * (n & 0x7Fu), j};
+}
+// the rounds requester rho gets in a trip of H helpers and n requesters
+RT_HD uint32_t coop_rounds(uint32_t rho, uint32_t H, uint32_t n, float rn) {
+    const CoopShare a = coop_assign(H, n, rn);             // (H mod n, H div n)
+    return a.j + (rho < a.q ? 1u : 0u);
+}
+// A trip's result word of a requester: the minimum over its accepted rounds of (offset, x draw, y draw),
+// all ones when none was accepted (an offset no trip reaches); the z draw is the requester's to repeat
+constexpr unsigned long long kCoopNone = ~0ull;
+RT_HD unsigned long long coop_pack(uint32_t j, uint32_t ux, uint32_t uy) {
+    return ((unsigned long long)j << 48) | ((unsigned long long)ux << 24) | (unsigned long long)uy;
+}
+// the take rule: the lowest accepted offset below c ends the loop after that round's draws, else the trip's
+// c rounds are consumed and the lane still needs a point
+RT_HD bool coop_take(unsigned long long word, uint32_t c, uint32_t& k, uint32_t& ux, uint32_t& uy) {
+    const uint32_t best = (uint32_t)(word >> 48);
+    if (best < c) {
+        k += 3 * (best + 1);
+        ux = (uint32_t)(word >> 24) & 0xFFFFFFu;
+        uy = (uint32_t)word & 0xFFFFFFu;
+        return true;
+    }
+    k += 3 * c;
+    return false;
+}
+
 template <class R>
 RT_HD V3<R> random_in_unit_disk(Rng<R>& g) {                    // math.js:27-31
     int64_t x, y;                                                 // exact, as random_in_unit_sphere

@@ -366,20 +366,98 @@ template <class R> struct NeeCtx : LightCtx<R> {
 struct NoLightCtx { template <class... A> RT_HD NoLightCtx(A&&...) {} };
 template <class R, bool LIT, bool NEE = false>
 using LightState = std::conditional_t<NEE, NeeCtx<R>, std::conditional_t<LIT, LightCtx<R>, NoLightCtx>>;
+// RT_COOP_SPHERE (pt_core.h): random_in_unit_sphere for the lanes with `need`, its rejection rounds evaluated by
+// every lane of the wave that reaches this call — requester or not: missed rays, Dielectric hits and lanes whose
+// point is found help the lanes still looking.  The point and g.k afterwards are the sequential loop's (the first
+// accepted round r >= 0 of draws k0+3r .. k0+3r+2, then k = k0 + 3 (r+1)); lanes without `need` get (0, 0, 0) and
+// keep their k.  slots: the wave's 64 x {(key, k), result word} in LDS (kCoopSlotBytes each).  After each requester's
+// own first round, a trip:
+//   1. requester rho (its rank among the lanes that need, by mbcnt: holes in EXEC need no special case) writes
+//      (key, k) and kCoopNone at slot rho;
+//   2. helper h (its rank among the active lanes) reads slot q's stream, evaluates the round at offset j
+//      (coop_assign) and, if that point is accepted, ds_min's coop_pack(j, x, y) into slot q's word;
+//   3. the requester reads its word: coop_take.  The z draw is not handed over: the requester repeats it.
+// The steps are ordered as pool_item orders its partials: a wave's LDS operations complete in program order, the
+// wave-local fence and wave_barrier keep the compiler from moving them.  `while (N)` is wave-uniform, and every
+// trip consumes at least one round of every requester, so the loop ends when the slowest sequential loop would.
+constexpr int kCoopSlotBytes = 16;
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ uint32_t coop_rank(uint64_t mask) {       // the active lanes of `mask` below this one
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+}
+template <class R>
+__device__ __forceinline__ V3<R> unit_sphere_point(Rng<R>& g, bool need, unsigned long long* slots) {
+    uint32_t ux = 1u << 23, uy = 1u << 23, uz = 1u << 23;             // (0, 0, 0)
+    // the first round is the lane's own: half of the requesters end here, and the hand-off costs more than a round
+    // (sharing the first trip too measured -0.3 % where this form gains 1.5 %)
+    if (need) {
+        need = !sphere_round(g.key, g.k, ux, uy, uz);
+        g.k += 3;
+    }
+    uint64_t N = __ballot(need);
+    while (N) {
+        const uint64_t E = __ballot(true);
+        const uint32_t n = (uint32_t)__popcll(N), H = (uint32_t)__popcll(E);
+        const uint32_t rho = coop_rank(N);
+        const float rn = coop_rcp(n);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (need) {
+            slots[2 * rho] = ((unsigned long long)g.k << 32) | g.key;
+            slots[2 * rho + 1] = kCoopNone;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const CoopShare a = coop_assign(coop_rank(E), n, rn);
+        const unsigned long long stream = slots[2 * a.q];
+        uint32_t hx, hy, hz;
+        if (sphere_round((uint32_t)stream, (uint32_t)(stream >> 32) + 3 * a.j, hx, hy, hz))
+            __hip_atomic_fetch_min(slots + 2 * a.q + 1, coop_pack(a.j, hx, hy), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (need && coop_take(slots[2 * rho + 1], coop_rounds(rho, H, n, rn), g.k, ux, uy)) {
+            Rng<R> gz{g.key, g.k - 1};
+            uz = gz.next_u24();
+            need = false;
+        }
+        N = __ballot(need);
+    }
+    return mk((R)((int)ux - (1 << 23)) * (R)0x1p-23, (R)((int)uy - (1 << 23)) * (R)0x1p-23, (R)((int)uz - (1 << 23)) * (R)0x1p-23);
+}
+#endif
+// where the cooperative form is compiled in: binary64 with the lean grid kernel's feature set (pool_item of
+// trace_pool_lds_kernel<double, *, ACC_GRID_LDS_LEAN>, and rt_shade_segments' variant 2), on the device
+template <class R, int FEAT>
+constexpr bool coop_sphere() {
+#if RT_COOP_SPHERE && defined(__HIP_DEVICE_COMPILE__)
+    return sizeof(R) == 8 && FEAT == feat_of<ACC_GRID_LDS_LEAN>();
+#else
+    return false;
+#endif
+}
+// coop: unit_sphere_point's LDS slots of this wave (nullptr, and every other instantiation: each lane's own loop)
 template <class R, int FEAT = F_ALL, int ACC = ACC_BRUTE>
 RT_HD bool shade_segment(const SceneView<R>& sc, const Closest<R>& c, V3<R>& o, V3<R>& d, V3<R>& T, int& depth,
-                         Rng<R>& g, V3<R>& L, const MatRec<R>* mats = nullptr, LightCtx<R>* lc = nullptr) {
+                         Rng<R>& g, V3<R>& L, const MatRec<R>* mats = nullptr, LightCtx<R>* lc = nullptr,
+                         unsigned long long* coop = nullptr) {
     bool done = true;
     L = mk<R>(0, 0, 0);
     const bool hit = c.kind != HIT_NONE;
     Hit<R> h{};
     MatRec<R> m{};
     V3<R> p = mk<R>(0, 0, 0);
+    const bool shared = coop_sphere<R, FEAT>() && coop != nullptr;
     if (hit) {
         h = hit_record<R, FEAT>(sc, o, d, c);
         m = mats ? mats[h.mat] : sc.mats[h.mat];            // mats: an LDS copy (RT_MAT_LDS A/B)
-        if (m.type <= 1) p = random_in_unit_sphere(g);                       // Lambertian / Metal's only draws
+        if (!shared && m.type <= 1) p = random_in_unit_sphere(g);            // Lambertian / Metal's only draws
     }
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (coop_sphere<R, FEAT>()) {
+        // ... drawn by the wave together: every lane here takes part (MatRec m{} has type 0 on a miss)
+        if (shared) p = unit_sphere_point(g, hit && m.type <= 1, coop);
+    }
+#endif
     // one normalize for every lane (see scatter): Lambertian's p, else the ray direction (Metal,
     // Dielectric, and a missed ray's skyGradient)
     const V3<R> unit = normalize(hit && m.type == 0 ? p : d);

@@ -440,7 +440,8 @@ void trace_pool_kernel(const TraceArgs<R> args, double* __restrict__ part, const
 template <class R, bool COUNT, int ACC>
 __device__ __forceinline__ void pool_item(const TraceArgs<R>& args, double* __restrict__ part, const int tiles,
                                           const int chunk, const unsigned pos, double* acc, BvhStack stk,
-                                          PixelResult& res, const int lane, const MatRec<R>* lmats = nullptr) {
+                                          PixelResult& res, const int lane, const MatRec<R>* lmats = nullptr,
+                                          unsigned long long* coop = nullptr) {
     const ImageParams& im = args.im;
     const SceneView<R>& sc = args.sc;
     const unsigned item = item_at(im, pos, tiles);       // pos: the queue's position
@@ -491,7 +492,7 @@ __device__ __forceinline__ void pool_item(const TraceArgs<R>& args, double* __re
             ++res.segments;
             ++isegs;
             V3<R> L;
-            waiting = shade_segment<R, feat_of<ACC>()>(sc, c, o, d, T, depth, g, L, lmats);
+            waiting = shade_segment<R, feat_of<ACC>()>(sc, c, o, d, T, depth, g, L, lmats, nullptr, coop);
             if constexpr (RT_ORIGIN_LEAVE && sizeof(R) == 8 && ACC == ACC_GRID_LDS_LEAN)
                 origin = !waiting && c.kind == HIT_SPHERE ? c.idx : -1;
             if (RT_PROFILE) res.cyc[1] += RT_TICK() - t1;
@@ -635,6 +636,12 @@ void trace_pool_lds_kernel(const TraceArgs<R> args, double* __restrict__ part, c
         lmats = mm;
     }
 #endif
+    // RT_COOP_SPHERE: the waves' hand-off slots of unit_sphere_point (pt_path.h; kernel_select.h counts them)
+    unsigned long long* coop = nullptr;
+    if constexpr (coop_lds_bytes<R, ACC>() > 0) {
+        __shared__ unsigned long long coop_all[coop_lds_bytes<R, ACC>() / 8];
+        coop = coop_all + wave * (64 * kCoopSlotBytes / 8);
+    }
     __syncthreads();
     uint32_t* queue = g_pool_queue + 2 * qi;
     PixelResult res{0, 0, {0, 0, 0}, {0, 0, 0}};
@@ -645,7 +652,7 @@ void trace_pool_lds_kernel(const TraceArgs<R> args, double* __restrict__ part, c
         if (lane == 0) it = __hip_atomic_fetch_add(queue, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         it = (uint32_t)__builtin_amdgcn_readfirstlane((int)it);
         if (it >= (uint32_t)items) break;
-        pool_item<R, COUNT, ACC>(args, part, tiles, chunk, it, acc, stk, res, lane, lmats);
+        pool_item<R, COUNT, ACC>(args, part, tiles, chunk, it, acc, stk, res, lane, lmats, coop);
     }
     add_totals<ACC>(args.c, res, lane);
     if (lane == 0) {
@@ -1481,7 +1488,14 @@ __global__ __launch_bounds__(64) void shade_segments_kernel(const SceneView<R> s
     int depth = depth0;
     Work w{0, 0, 0, 0, 0, 0};
     const Closest<R> c = closest_hit_acc<R, ACC>(sc, o, d, w, stk);
-    const bool done = shade_segment<R, FEAT, ACC>(sc, c, o, d, T, depth, g, L);
+    // the lean grid kernel's feature set in binary64: its wave-cooperative unit-sphere draw (RT_COOP_SPHERE); the
+    // lanes past n have left, as the lanes of a pool wave that wait or have run out of items
+    unsigned long long* coop = nullptr;
+    if constexpr (coop_sphere<R, FEAT>()) {
+        __shared__ unsigned long long coop_slots[64 * kCoopSlotBytes / 8];
+        coop = coop_slots;
+    }
+    const bool done = shade_segment<R, FEAT, ACC>(sc, c, o, d, T, depth, g, L, nullptr, nullptr, coop);
     double* f = out_f + 12 * r;
     f[0] = (double)o.x; f[1] = (double)o.y; f[2] = (double)o.z;
     f[3] = (double)d.x; f[4] = (double)d.y; f[5] = (double)d.z;
